@@ -3,6 +3,7 @@
 BoT-SORT + OSNet-x0.25 ReID inside update, 64 detections x 256 live tracks, 1080p frames.
 
   python bench.py --gpus N --steps K --warmup W [--streams S] [--groups G] [--mode embs|reid] [--reid-mode 0|1|2]
+                  [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch = every one of the S streams of this GPU
 advances by one frame (ReID crop/resize/normalise + OSNet + cost matrices + assignment + Kalman +
@@ -15,10 +16,16 @@ group's tracker step (one workgroup per stream: latency-bound, few CUs) overlaps
 kernels (+4 % at G = 2); the default keeps one group so that the HIP-event launch durations behind
 `roofline` are those of kernels running alone and agree with the rocprofv3 per-kernel averages.
 
-Extra objects on the JSON line (N = 1): `roofline`, `cpu_baseline` (the contract: kind = "reference" when the reference's own classes
+A plain run does only what the headline needs: set up, warm up, time the K steps, write the outputs of the last timed step when
+`--dump-outputs DIR` asks (dump_outputs: the result rows and row counts every stream's caller receives, as float .npy files; the
+inputs are seeded, so two builds given the same arguments can be compared output for output), print the line with `roofline`
+(taken from the timed steps' own HIP events).  Everything else runs only with `--full`.
+
+Extra objects on the JSON line with --full (N = 1): `cpu_baseline` (the contract: kind = "reference" when the reference's own classes
 can be imported -- /root/reference in the build container, the byte-compiled oracle/_ref/ (oracle/make_ref.py) on the GPU box -- else
 "port" = the oracle; the other one is attached beside it), `cpu_side_baselines` (the reference's tracker math with supplied embeddings
-and the reference ByteTrack on BASELINE configuration 1, bounded samples), `tracker_math_m1` (embeddings supplied), and
+and the reference ByteTrack on BASELINE configuration 1, bounded samples), `tracker_math_m1` (embeddings supplied), the gates in
+`config` (ids vs the oracle, the all-stream invariants, embeddings vs the fp32 oracle), `fp16_family_line` and
 `other_configs` -- short side measurements of BASELINE.json's configurations 3 (DeepOCSORT + OSNet_x1_0, 128 x 512) and 5 (StrongSORT +
 CLIP-ReID ViT-B/16, 256 x 1024, 4K) through tools/config_bench.py, each with its ReID roofline fraction and an embedding parity gate;
 they are never part of `value`.
@@ -31,8 +38,8 @@ streams r*S .. r*S+S-1, S = --streams per GPU: weak scaling) with no data-path c
 barrier + device synchronisation on both sides and the elapsed time is the MAX over ranks (all_reduce); the per-frame result
 rows are gathered to rank 0 once after the timed loop (`gather_results`: RCCL all_gather of a few hundred KB), timed and
 reported separately as `gather_ms`.  Rank 0 keeps the id parity gate at every N -- ids of streams 0, S / 2 and S - 1 of its shard
-against the oracle (the first, a middle and the last workgroup / crop range of the timed launch) -- ; the CPU timing baseline runs at
-N = 1 only (the contract).
+against the oracle (the first, a middle and the last workgroup / crop range of the timed launch) with --full -- ; the CPU timing
+baseline runs at N = 1 only (the contract).
 
 `--stub-tracker --backend gloo` is a TEST seam (tests/test_bench_dist.py): the same launch / sharding / barrier / all_reduce /
 gather / JSON code runs on CPU processes with a trivial stand-in for the device handle, so the N > 1 control flow is covered
@@ -112,6 +119,10 @@ def parse(argv=None):
                     help="reid: ReID inside update (headline, M2); embs: embeddings supplied (tracker math only, M1)")
     ap.add_argument("--reid-mode", type=int, default=int(os.environ.get("BOXMOT_REID_MODE", "2")),
                     help="0: per-layer fp32 kernels, 1: fused fp16 MFMA kernels, 2: fused fp32-grade kernels")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR (rows.npy, row_counts.npy; rank 0's streams)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baseline, the gates against the oracle and the side measurements (off: only the headline)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-m1", action="store_true", help="skip the tracker-math-only (embeddings supplied) side measurement")
     ap.add_argument("--no-side-configs", action="store_true",
@@ -129,7 +140,10 @@ def parse(argv=None):
     ap.add_argument("--backend", choices=("nccl", "gloo"), default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL)")
     ap.add_argument("--stub-tracker", action="store_true",
                     help="TEST ONLY: run the N > 1 control flow on CPU with a stand-in for the device handle (no measurement)")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def log(msg):
@@ -508,6 +522,28 @@ def reid_parity_gates(sd, reid_mode):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 * 2**20
+
+
+def dump_outputs(out_dir, rows, counts):
+    """What the last timed step returned to the caller of each stream: rows.npy (S, max_dets, 8) float32 -- the result rows
+    [x1, y1, x2, y2, id, conf, cls, det_ind], zero past the stream's count -- and row_counts.npy (S,) float64.  Past 64 MB a fixed
+    (seed 0) sample of the streams is written and streams.npy names them."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    S, nd = rows.shape[:2]
+    rows = np.where(np.arange(nd)[None, :, None] < counts[:, None, None], rows, 0).astype(np.float32)
+    per_stream = rows[0].nbytes + 16                 # rows + count + stream index
+    if S * per_stream > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(S, DUMP_LIMIT_BYTES // per_stream, replace=False))
+        rows, counts = rows[keep], counts[keep]
+        np.save(out / "streams.npy", keep.astype(np.float64))
+    else:
+        (out / "streams.npy").unlink(missing_ok=True)
+    np.save(out / "rows.npy", rows)
+    np.save(out / "row_counts.npy", counts.astype(np.float64))
+
+
 class StubStreams:
     """TEST-ONLY stand-in for MultiStreamBotSort (--stub-tracker): same call surface over host tensors, every detection becomes
     one output row [box, id = index + 1, conf, cls, index].  It exists so that the launch / sharding / barrier / all_reduce /
@@ -703,9 +739,11 @@ def main(argv=None):
         r_ms, r_n = m.reid_kernel_ms()
         reid_ms += r_ms
         reid_launches += r_n
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, d_out[T - 1].cpu().numpy(), d_out_n[T - 1].cpu().numpy())
+        log(f"outputs of the last timed step written to {a.dump_outputs}")
 
     # ---- result gather (the only collective of the path), after the timed loop; timed on its own ----
-    out_h, out_n_h = d_out.cpu().numpy(), d_out_n.cpu().numpy()
     gather_ms, gathered_ok = None, None
     if use_dist:
         from boxmot_amd.streams import gather_results
@@ -764,12 +802,13 @@ def main(argv=None):
         for m in groups:
             m.close()
         groups = []
-        if stub:
+        if stub or not a.full:
             a.no_m1 = a.no_side_configs = a.no_cpu_baseline = True
         if not a.no_cpu_baseline:
             # the CPU path on stream 0: at N = 1 timed as the CPU baseline (the contract); at every N the id parity gate -- on
             # streams 0, S/2 and S - 1 of rank 0's shard (the first, a middle and the LAST workgroup / crop range of the launch the
             # headline times: an indexing fault at high stream or crop indices fails the gate)
+            out_h, out_n_h = d_out.cpu().numpy(), d_out_n.cpu().numpy()
             cb, rows = cpu_baseline(sd, a.mode, a.cpu_frames if world == 1 else min(a.cpu_frames, 4))
             if world == 1:
                 res["cpu_baseline"] = cb
@@ -798,7 +837,7 @@ def main(argv=None):
                 res["config"].update(reid_parity_gates(sd, a.reid_mode))
         # the headline with its gates, as soon as they exist (stderr; the ONE stdout line stays last): what follows are side
         # measurements under a wall budget, none of which can change or lose these fields
-        log("headline (gates done): " + json.dumps({k: res[k] for k in res if k not in ("tracker_math_m1", "other_configs", "fp16_family_line")}))
+        log("headline" + ("" if a.no_cpu_baseline else " (gates done)") + ": " + json.dumps({k: res[k] for k in res if k not in ("tracker_math_m1", "other_configs", "fp16_family_line")}))
         if world == 1 and a.mode == "reid" and not a.no_m1:
             try:
                 res["tracker_math_m1"] = m1_tracker_only(kw, dev, rank, a.streams)

@@ -32,12 +32,20 @@ SOURCE_ROOT = Path("/root/reference")
 COMPILED_ROOT = Path(__file__).resolve().parent / "_ref"
 
 
+def _source_present() -> bool:
+    """The reference source tree can be read.  os.path.exists: a location this user may not enter counts as absent instead of
+    raising PermissionError (Path.exists raises it)."""
+    import os
+
+    return os.path.exists(SOURCE_ROOT / "boxmot" / "trackers" / "bbox" / "botsort" / "botsort.py")
+
+
 def _pick_root() -> Path:
     """The source tree when it is mounted; otherwise the byte-compiled copy (oracle/make_ref.py).  BOXMOT_ORACLE_REF=compiled forces
     the compiled copy (the test of the fallback in the build container)."""
     import os
 
-    have_src = (SOURCE_ROOT / "boxmot" / "trackers" / "bbox" / "botsort" / "botsort.py").exists()
+    have_src = _source_present()
     if have_src and os.environ.get("BOXMOT_ORACLE_REF", "") != "compiled":
         return SOURCE_ROOT
     if _compiled_usable():
@@ -67,7 +75,7 @@ REFERENCE_ROOT = _pick_root()
 def reference_kind():
     """"source" (/root/reference mounted), "compiled" (oracle/_ref/) or None."""
     if REFERENCE_ROOT == SOURCE_ROOT:
-        return "source" if (SOURCE_ROOT / "boxmot" / "trackers" / "bbox" / "botsort" / "botsort.py").exists() else None
+        return "source" if _source_present() else None
     return "compiled" if _compiled_usable() else None
 
 

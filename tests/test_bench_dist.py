@@ -86,3 +86,50 @@ def test_force_dist_runs_the_collectives_with_one_rank():
     assert p.returncode == 0, p.stderr[-3000:]
     d = _json_line(p.stdout)
     assert d["n_gpus"] == 1 and d["config"]["gather"]["complete_on_rank0"] is True and d["gather_ms"] > 0
+
+
+def test_dump_outputs_writes_the_last_timed_step_the_same_every_run(tmp_path):
+    """`--dump-outputs DIR`: the rows and row counts of the last timed step (frame W + K - 1) as float .npy files, zero past each
+    stream's count, identical from run to run (seeded inputs).  The stub echoes that frame's detections, so the boxes are known."""
+    import numpy as np
+
+    sys.path.insert(0, str(ROOT))
+    from boxmot_amd.scenario import Scenario
+    got = []
+    for i in range(2):
+        out = tmp_path / str(i)
+        p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", *ARGS, "--dump-outputs", str(out)], capture_output=True,
+                           text=True, timeout=300, env=_env(), cwd=str(ROOT))
+        assert p.returncode == 0, p.stderr[-3000:]
+        d = _json_line(p.stdout)
+        assert d["steps"] == 4 and d["ms_per_step"] > 0
+        rows, counts = np.load(out / "rows.npy"), np.load(out / "row_counts.npy")
+        assert rows.dtype == np.float32 and counts.dtype == np.float64 and rows.shape == (3, 256, 8) and counts.shape == (3,)
+        assert not (out / "streams.npy").exists()
+        got.append((rows, counts))
+    assert np.array_equal(got[0][0], got[1][0]) and np.array_equal(got[0][1], got[1][1])
+    rows, counts = got[0]
+    for s in range(3):
+        sc = Scenario(64, 256, 1920, 1080, 512, stream=s, random_image=False)
+        dets = [sc.frame(t, with_embs=False)[0] for t in range(2 + 4)][-1]
+        n = len(dets)
+        assert counts[s] == n and np.array_equal(rows[s, :n, :4], dets[:, :4]) and not rows[s, n:].any()
+
+
+def test_dump_outputs_samples_streams_past_the_size_limit(tmp_path, monkeypatch):
+    import numpy as np
+
+    sys.path.insert(0, str(ROOT))
+    import bench
+    S, nd = 40, 4
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 10 * (nd * 8 * 4 + 16))
+    rows = np.arange(S * nd * 8, dtype=np.float32).reshape(S, nd, 8) + 1
+    counts = np.full(S, 3, dtype=np.int32)
+    bench.dump_outputs(tmp_path, rows, counts)
+    keep = np.load(tmp_path / "streams.npy").astype(np.int64)
+    assert len(keep) == 10 and (np.diff(keep) > 0).all()
+    got = np.load(tmp_path / "rows.npy")
+    assert np.array_equal(got[:, :3], rows[keep, :3]) and not got[:, 3:].any()
+    assert np.array_equal(np.load(tmp_path / "row_counts.npy"), np.full(10, 3.0))
+    bench.dump_outputs(tmp_path, rows[:2], counts[:2])              # under the limit: all streams, no stale sample index
+    assert not (tmp_path / "streams.npy").exists() and np.load(tmp_path / "rows.npy").shape == (2, nd, 8)

@@ -11,7 +11,7 @@
 #   fast       python -m pytest tests -m "gpu and fast" (tests/conftest.py FAST_GPU: about a minute) -> pytest_fast.log
 #   costs      tests/test_gpu_cost_values.py (association cost values vs the reference's matrices) -> pytest_costs.log
 #   reid       the ReID GPU tests only                                        -> pytest_reid.log
-#   bench      default bench.py                                               -> bench.json / bench.err
+#   bench      bench.py --full (CPU baseline, gates, side lines)              -> bench.json / bench.err
 #   benchq     bench.py without CPU baseline / side lines (quick)             -> benchq.json
 #   trace      rocprofv3 --kernel-trace --stats of `bench.py --no-cpu-baseline --no-side-configs --no-m1` -> kernel_stats.txt
 #   traffic    FETCH_SIZE and WRITE_SIZE, separate --pmc passes, on tools/reid_microbench.py 4096 crops (mode $REID_MODE)  -> pmc_traffic.txt
@@ -46,7 +46,7 @@ for step in "$@"; do
     fast)    timeout 400 python -m pytest tests -q -m "gpu and fast" --durations=8 > $O/pytest_fast.log 2>&1; echo "pytest rc=$?" >> $O/pytest_fast.log; tail -n 16 $O/pytest_fast.log | cut -c1-220 ;;
     costs)   timeout 400 python -m pytest tests/test_gpu_cost_values.py -q -s > $O/pytest_costs.log 2>&1; echo "pytest rc=$?" >> $O/pytest_costs.log; grep -E "max \||passed|failed|rc=|Error" $O/pytest_costs.log | cut -c1-220 ;;
     reid)    timeout 600 python -m pytest tests/test_gpu_reid.py -q -s --maxfail=10 > $O/pytest_reid.log 2>&1; echo "pytest rc=$?" >> $O/pytest_reid.log; grep -E "calibrated|passed|failed|rc=" $O/pytest_reid.log | cut -c1-220 ;;
-    bench)   timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; tail -c 1500 $O/bench.json; echo ;;
+    bench)   timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; tail -c 1500 $O/bench.json; echo ;;
     benchq)  timeout 400 python bench.py --no-cpu-baseline --no-side-configs --no-m1 --reid-mode $MODE > $O/benchq_m$MODE.json 2> $O/benchq.err; tail -c 900 $O/benchq_m$MODE.json; echo ;;
     trace)   (cd /tmp && export TMPDIR=/tmp && timeout 500 rocprofv3 --kernel-trace --stats -d $O/kt -o bench -- python $R/bench.py --no-cpu-baseline --no-side-configs --no-m1 --reid-mode $MODE > $O/bench_kt.json 2> $O/bench_kt.err)
              stamp > $O/kernel_stats_m$MODE.txt
