@@ -73,6 +73,19 @@ inline void emu_complete_copies(bool all) {
     }
     v.resize(keep);
 }
+// counted wait (s_waitcnt vmcnt(n)): this thread's copies land in issue order, except the n youngest, which stay in flight
+inline void emu_complete_copies_but(int n) {
+    auto& v = emu_pending();
+    long mine = 0;
+    for (const auto& c : v) mine += c.tid == threadIdx.x;
+    long done = 0;
+    size_t keep = 0;
+    for (size_t k = 0; k < v.size(); ++k) {
+        if (v[k].tid == threadIdx.x && done < mine - n) { std::memcpy(v[k].dst, v[k].src, v[k].bytes); ++done; }
+        else v[keep++] = v[k];
+    }
+    v.resize(keep);
+}
 #endif
 
 #ifndef EMU_PTHREADS
@@ -415,4 +428,21 @@ inline auto emu_ds_read_tr16_b64(const H* p) {
 #define BM_GLDS16(gptr, lds_wave_base, lane) std::memcpy(reinterpret_cast<unsigned char*>(lds_wave_base) + 16 * (lane), (gptr), 16)
 #define BM_GLDS4(gptr, lds_wave_base, lane) std::memcpy(reinterpret_cast<unsigned char*>(lds_wave_base) + 4 * (lane), (gptr), 4)
 #define BM_WAIT_VM0() ((void)0)
+#endif
+
+// k_gemm_f16_256's phase synchronisation (gemm_f16.hpp): both barriers are workgroup barriers (the LDS reads before the phase
+// barrier are complete when the emulated read returns), and its counted copy waits -- vmcnt(6) / vmcnt(0) -- complete all of the
+// thread's pending copies but the 6 / 0 youngest.  EMU_GEMM_WAIT6_KEEP (default 6) is the negative control of that count: a build
+// that leaves 7 or 8 copies in flight there must read a tile's operands before they have landed.
+#ifndef EMU_GEMM_WAIT6_KEEP
+#define EMU_GEMM_WAIT6_KEEP 6
+#endif
+#define BM_GEMM_PHASE_SYNC() __syncthreads()
+#define BM_GEMM_BARRIER() __syncthreads()
+#if defined(EMU_DEFER_GLDS) && !defined(EMU_PTHREADS)
+#define BM_GEMM_WAIT_COPIES_6() emu_complete_copies_but(EMU_GEMM_WAIT6_KEEP)
+#define BM_GEMM_WAIT_COPIES_0() emu_complete_copies_but(0)
+#else
+#define BM_GEMM_WAIT_COPIES_6() ((void)0)
+#define BM_GEMM_WAIT_COPIES_0() ((void)0)
 #endif
