@@ -135,6 +135,9 @@ SIGNATURES = {
     "boxmot_hip_botsort_status": (_I, [_VP, _VP, _I]),
     "boxmot_hip_botsort_set_reid_blob": (_I, [_VP, _VP, ctypes.c_long]),
     "boxmot_hip_botsort_set_reid_mode": (_I, [_VP, _I]),
+    "boxmot_hip_botsort_set_frame_sizes": (_I, [_VP, _VP, _VP, _I]),
+    "boxmot_hip_deepocsort_set_frame_sizes": (_I, [_VP, _VP, _VP, _I]),
+    "boxmot_hip_strongsort_set_frame_sizes": (_I, [_VP, _VP, _VP, _I]),
     "boxmot_hip_botsort_last_reid_time_ms": (_I, [_VP, c_double_p]),
     "boxmot_hip_botsort_last_reid_preprocess_time_ms": (_I, [_VP, c_double_p]),
     "boxmot_hip_botsort_last_reid_process_time_ms": (_I, [_VP, c_double_p]),
@@ -189,6 +192,8 @@ SIGNATURES = {
     "boxmot_hip_reid_set_preprocess": (_I, [_VP, ctypes.c_char_p]),
     "boxmot_hip_reid_compute_features": (_I, [_VP, _VP, _I, _I, _I, _VP, _I, _I, _VP, _I]),
     "boxmot_hip_reid_preprocess": (_I, [_VP, _VP, _I, _I, _I, _VP, _I, _I, _VP]),
+    "boxmot_hip_reid_compute_features_batch": (_I, [_VP, _VP, _VP, _VP, _I, _VP, _VP, _I, _I, _VP, _I]),
+    "boxmot_hip_reid_preprocess_batch": (_I, [_VP, _VP, _VP, _VP, _I, _VP, _VP, _I, _I, _VP]),
     "boxmot_hip_reid_last_time_ms": (_I, [_VP, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "boxmot_hip_botsort_update_batch_frames": (_I, [_VP, _I, _VP, _VP, _VP, _I, _VP, _I, _I, _VP, _I, _VP]),
     "boxmot_hip_deepocsort_stream": (_VP, [_VP]),
@@ -206,6 +211,7 @@ SIGNATURES = {
     "boxmot_hip_sof_keypoints": (_I, [_VP, _I, _VP, _I, c_int_p]),
     "boxmot_hip_sof_debug_map": (_I, [_VP, _I, _I, _VP, _I, c_int_p, c_int_p]),
     "boxmot_hip_ingest_create": (_VP, [_I, _I, _I, _I]),
+    "boxmot_hip_ingest_create_sized": (_VP, [_I, _I, _VP, _VP]),
     "boxmot_hip_ingest_destroy": (None, [_VP]),
     "boxmot_hip_ingest_host_ptr": (_VP, [_VP, _I, _I]),
     "boxmot_hip_ingest_device_frames": (_VP, [_VP, _I]),

@@ -7,6 +7,7 @@
 
 #include <cmath>
 #include <cstring>
+#include <map>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -246,9 +247,22 @@ struct BoxMOTHipReID : DeviceBound {
     bool obb = false;                            // the boxes of the last reid_stage were oriented (5 / 7 / 9 columns)
     int staged_n = -1, staged_rows = 0, staged_cols = 0;      // boxmot_reid_capi_preprocess -> process -> postprocess
     bool staged_done = false;
+    // boxmot_hip_reid_*_batch: one device buffer per image of the call, the table of their pointers, the {W, H} table the `_sized`
+    // kernels read (uploaded when a size differs from the one the table holds), and the crop -> image table of the pass.
+    // A buffer grows to the largest image seen at its index and is never shrunk: a caller that varies the order of its frames
+    // ends up with a buffer of its largest frame at every index (freed with the handle).
+    std::vector<uint8_t*> batch_bufs;
+    std::vector<size_t> batch_bytes;
+    std::vector<int> batch_dims;                 // host copy of d_batch_dims
+    const uint8_t** d_batch_frames = nullptr;
+    int* d_batch_dims = nullptr;
+    int* d_batch_crop_stream = nullptr;          // [max_crops]
     ~BoxMOTHipReID() {
         engine.reset();
         for (void* p : owned) (void)hipFree(p);
+        for (uint8_t* p : batch_bufs) if (p) (void)hipFree(p);
+        if (d_batch_frames) (void)hipFree(d_batch_frames);
+        if (d_batch_dims) (void)hipFree(d_batch_dims);
         if (d_frame) (void)hipFree(d_frame);
         if (stream) (void)hipStreamDestroy(stream);
     }
@@ -301,6 +315,7 @@ struct BoxMOTHipSof : DeviceBound {
 struct BoxMOTHipIngest : DeviceBound {
     int n_slots = 0, n_streams = 0, rows = 0, cols = 0;
     size_t frame_bytes = 0;
+    std::vector<size_t> offs;                       // [n_streams + 1]: byte offset of each stream's frame inside a slot (one allocation, one DMA)
     hipStream_t copy_stream = nullptr;
     std::vector<uint8_t*> h_slot, d_slot;           // [n_slots]: n_streams contiguous frames each
     std::vector<const uint8_t**> d_ptrs;            // [n_slots]: device table of n_streams frame pointers
@@ -359,6 +374,15 @@ struct BoxMOTHipBotSort : DeviceBound {
     bool cmc_with_fc_set = false;                // one update with a frame-counter preset that is NOT a per-class fan-out call (compat adapter's first
                                                  // real frame after empty ones): the estimator sees the frame as it does in the reference
     std::unique_ptr<BoxMOTHipSof> sof;
+    // per-stream frame sizes (boxmot_hip_botsort_set_frame_sizes): empty = one size per handle, taken from the calls' scalar
+    // arguments.  d_fs_dims is the {W, H} table the `_sized` crop kernels read (beside d_crop_stream; written when the sizes are
+    // set, not per frame); it is handed to the engine only when the sizes differ.  Handle-owned camera-motion estimation keeps one
+    // estimator per DISTINCT size; each is made for all S streams and serves the streams of its size under their own indices.
+    std::vector<int> fs_rows, fs_cols;
+    int* d_fs_dims = nullptr;
+    bool fs_mixed = false;
+    std::map<std::pair<int, int>, std::unique_ptr<BoxMOTHipSof>> sof_by_size;
+    std::map<std::pair<int, int>, std::unique_ptr<BoxMOTHipEcc>> ecc_by_size;
     int* d_crop_count = nullptr;
     int* d_crop_stream = nullptr;
     float* d_crop_boxes = nullptr;
@@ -453,6 +477,10 @@ struct StreamIo : DeviceBound {
     bool stream_exposed = false;        // *_stream() was handed out: the caller may order its inputs on `stream` -- every ReID pass waits for it
     int* d_ndets_step[2] = {};          // [S] each: the detection counts a bounded step reads (-1 everywhere after a bound overflow)
     const int* step_ndets = nullptr;    // what the frame step of the current step_device_frames call takes as n_dets
+    // per-stream frame sizes (boxmot_hip_{deepocsort,strongsort}_set_frame_sizes; as BoxMOTHipBotSort::fs_rows): empty = one size per handle
+    std::vector<int> fs_rows, fs_cols;
+    int* d_fs_dims = nullptr;           // [S][2] {W, H}: handed to the engine only when the sizes differ
+    bool fs_mixed = false;
     ~StreamIo() {
         if (reid_stream) (void)hipStreamSynchronize(reid_stream);
         if (stream) (void)hipStreamSynchronize(stream);
@@ -751,6 +779,11 @@ void run_reid(BoxMOTHipBotSort* h, int s0, int n_streams, const float* d_dets, c
               const uint8_t* const* d_frames, int rows, int cols, float* d_embs, hipStream_t st = nullptr) {
     if (!h->reid) throw std::runtime_error("boxmot_hip: with_reid=1 and no embeddings supplied, but no ReID weights are loaded");
     if (!st) { st = h->stream; h->engine_on_main = true; }
+    struct DimsScope { bm::ReidEngine* e; ~DimsScope() { e->set_frame_dims(nullptr); } } dims_scope{h->reid.get()};
+    if (!h->fs_rows.empty()) {      // per-stream sizes: the table when they differ, else the one size as the scalars (the launches of today)
+        rows = h->fs_rows[0]; cols = h->fs_cols[0];
+        h->reid->set_frame_dims(h->fs_mixed ? h->d_fs_dims : nullptr);
+    }
     BM_HIP(hipMemsetAsync(h->d_crop_count, 0, 4, st));
     hipLaunchKernelGGL(build_crop_list_kernel, dim3(n_streams), dim3(256), 0, st, d_dets, d_ndets, h->nd,
                        h->cfg.track_high_thresh, h->d_crop_count, h->d_crop_stream, h->d_crop_boxes, h->d_crop_row, s0);
@@ -793,6 +826,17 @@ std::string take_status(hipStream_t stream, int* d_status, int s0, int n, const 
 
 void upload_frame(BoxMOTHipBotSort* h, int s, const uint8_t* image, int rows, int cols, int channels) {
     if (channels != 3) throw std::runtime_error("boxmot_hip: ReID needs a 3-channel uint8 BGR image");
+    if (!h->fs_rows.empty()) {      // per-stream sizes: one buffer per stream of that stream's size (the scalar arguments are not used)
+        const size_t sbytes = (size_t)h->fs_rows[s] * h->fs_cols[s] * 3;
+        if (h->frame_bufs[s] == nullptr) {
+            void* p = nullptr;
+            BM_HIP(hipMalloc(&p, sbytes));
+            h->frame_bufs[s] = static_cast<uint8_t*>(p);
+            BM_HIP(hipMemcpy(h->d_frames, h->frame_bufs.data(), h->S * sizeof(uint8_t*), hipMemcpyHostToDevice));
+        }
+        BM_HIP(hipMemcpyAsync(h->frame_bufs[s], image, sbytes, hipMemcpyHostToDevice, h->stream));
+        return;
+    }
     const size_t bytes = (size_t)rows * cols * 3;
     if (h->frame_bufs[s] == nullptr || bytes != h->frame_bytes) {
         if (h->frame_bytes != 0 && bytes != h->frame_bytes)
@@ -932,6 +976,35 @@ struct StreamIn {
     const uint8_t* image;
 };
 
+// The estimator that owns stream s: the handle's one estimator (one frame size per handle, from the call's arguments), or -- with
+// per-stream sizes -- the estimator of that stream's size, made when a stream of the size is first estimated.
+BoxMOTHipSof* sof_of(BoxMOTHipBotSort* h, int s, int image_rows, int image_cols) {
+    if (h->fs_rows.empty()) {
+        if (!h->sof) {
+            h->sof.reset(new BoxMOTHipSof());
+            sof_init(h->sof.get(), h->S, image_rows, image_cols, 0.15, 8, 0.2, 3.0, h->stream);
+        }
+        if (h->sof->rows != image_rows || h->sof->cols != image_cols) throw std::runtime_error("boxmot_hip: frame size changed between updates");
+        return h->sof.get();
+    }
+    auto& e = h->sof_by_size[{h->fs_rows[s], h->fs_cols[s]}];
+    if (!e) { e.reset(new BoxMOTHipSof()); sof_init(e.get(), h->S, h->fs_rows[s], h->fs_cols[s], 0.15, 8, 0.2, 3.0, h->stream); }
+    return e.get();
+}
+BoxMOTHipEcc* ecc_of(BoxMOTHipBotSort* h, int s, int image_rows, int image_cols) {
+    if (h->fs_rows.empty()) {
+        if (!h->ecc) {
+            h->ecc.reset(new BoxMOTHipEcc());
+            ecc_init(h->ecc.get(), h->S, image_rows, image_cols, 0.15, 1e-5, 100, h->stream);
+        }
+        if (h->ecc->rows != image_rows || h->ecc->cols != image_cols) throw std::runtime_error("boxmot_hip: frame size changed between updates");
+        return h->ecc.get();
+    }
+    auto& e = h->ecc_by_size[{h->fs_rows[s], h->fs_cols[s]}];
+    if (!e) { e.reset(new BoxMOTHipEcc()); ecc_init(e.get(), h->S, h->fs_rows[s], h->fs_cols[s], 0.15, 1e-5, 100, h->stream); }
+    return e.get();
+}
+
 // Shared host path: stage inputs of streams [s0, s0+n), run ReID if needed, step, read back.
 void host_update(BoxMOTHipBotSort* h, int s0, int n, const StreamIn* in, int det_cols, int emb_cols,
                  int image_rows, int image_cols, int image_channels, const int* list_sel, const int* fc_set,
@@ -1006,20 +1079,16 @@ void host_update(BoxMOTHipBotSort* h, int s0, int n, const StreamIn* in, int det
             if (image_channels != 3) throw std::runtime_error("boxmot_hip: cmc_method=sof needs a 3-channel uint8 BGR image");
             if (!d_frames_ext) upload_frame(h, s0 + k, in[k].image, image_rows, image_cols, image_channels);
         }
-        if (!h->sof) {
-            h->sof.reset(new BoxMOTHipSof());
-            sof_init(h->sof.get(), h->S, image_rows, image_cols, 0.15, 8, 0.2, 3.0, h->stream);
-        }
-        if (h->sof->rows != image_rows || h->sof->cols != image_cols) throw std::runtime_error("boxmot_hip: frame size changed between updates");
         for (int k = 0; k < n; ++k) {
             if (in[k].det_rows < 0) continue;
             const uint8_t* const* fp = (d_frames_ext ? d_frames_ext : h->d_frames) + (s0 + k);
+            BoxMOTHipSof* sof = sof_of(h, s0 + k, image_rows, image_cols);
             if (h->is_obb) {        // botsort.py:147-158: the estimator sees the enclosing boxes of the oriented detections
                 hipLaunchKernelGGL(obb_enclosing_boxes_kernel, dim3(1), dim3(256), 0, h->stream, h->d_dets, h->d_ndets, nd, h->d_cmc_boxes, s0 + k);
-                sof_run(h->sof.get(), s0 + k, 1, fp, h->d_cmc_boxes + (size_t)(s0 + k) * nd * 4, h->d_ndets + s0 + k, nd, 4,
+                sof_run(sof, s0 + k, 1, fp, h->d_cmc_boxes + (size_t)(s0 + k) * nd * 4, h->d_ndets + s0 + k, nd, 4,
                         h->h_warp.data() + (size_t)(s0 + k) * 6, nullptr);
             } else
-            sof_run(h->sof.get(), s0 + k, 1, fp, d_dets + (size_t)k * nd * DC, h->d_ndets + s0 + k, nd, DC,
+            sof_run(sof, s0 + k, 1, fp, d_dets + (size_t)k * nd * DC, h->d_ndets + s0 + k, nd, DC,
                     h->h_warp.data() + (size_t)(s0 + k) * 6, nullptr);
             h->h_warp_flag[s0 + k] = 1;
         }
@@ -1035,15 +1104,10 @@ void host_update(BoxMOTHipBotSort* h, int s0, int n, const StreamIn* in, int det
             if (image_channels != 3) throw std::runtime_error("boxmot_hip: cmc_method=ecc needs a 3-channel uint8 BGR image");
             if (!d_frames_ext) upload_frame(h, s0 + k, in[k].image, image_rows, image_cols, image_channels);
         }
-        if (!h->ecc) {
-            h->ecc.reset(new BoxMOTHipEcc());
-            ecc_init(h->ecc.get(), h->S, image_rows, image_cols, 0.15, 1e-5, 100, h->stream);
-        }
-        if (h->ecc->rows != image_rows || h->ecc->cols != image_cols) throw std::runtime_error("boxmot_hip: frame size changed between updates");
         for (int k = 0; k < n; ++k) {
             if (in[k].det_rows < 0) continue;
             const uint8_t* const* fp = (d_frames_ext ? d_frames_ext : h->d_frames) + (s0 + k);
-            ecc_run_one(h->ecc.get(), s0 + k, fp, h->h_warp.data() + (size_t)(s0 + k) * 6, nullptr);
+            ecc_run_one(ecc_of(h, s0 + k, image_rows, image_cols), s0 + k, fp, h->h_warp.data() + (size_t)(s0 + k) * 6, nullptr);
             h->h_warp_flag[s0 + k] = 1;
         }
     }
@@ -1251,6 +1315,36 @@ bool io_consume_warps(StreamIo* h) {
 // after a device-resident step: pending warps are consumed, and the host no longer knows the track counts (io_make_room asks)
 void io_clear_warps(StreamIo* h) { for (int s = 0; s < h->S; ++s) { h->h_warp_flag[s] = 0; h->h_used[s] = -1; } }
 
+// the per-stream size table is handed to the engine for one pass only
+struct IoDimsScope { bm::ReidEngine* e; ~IoDimsScope() { if (e) e->set_frame_dims(nullptr); } };
+
+// boxmot_hip_{deepocsort,strongsort}_set_frame_sizes: one (rows, cols) per stream; a stream that already has frames of another size
+// is an error naming the stream
+void io_set_frame_sizes(StreamIo* h, const int* image_rows, const int* image_cols, int n_streams) {
+    if (!image_rows || !image_cols) throw std::runtime_error("boxmot_hip: null argument");
+    if (n_streams != h->S) throw std::runtime_error("boxmot_hip: set_frame_sizes needs one (rows, cols) per stream of the handle (" + std::to_string(h->S) + ")");
+    for (int s = 0; s < h->S; ++s) {
+        if (image_rows[s] < 1 || image_cols[s] < 1) throw std::runtime_error("boxmot_hip: stream " + std::to_string(s) + ": frame dimensions must be positive");
+        const bool seen = h->frame_bufs[s] != nullptr || !h->fs_rows.empty();
+        const int r0 = h->fs_rows.empty() ? h->frame_rows : h->fs_rows[s], c0 = h->fs_cols.empty() ? h->frame_cols : h->fs_cols[s];
+        if (seen && (r0 != image_rows[s] || c0 != image_cols[s]))
+            throw std::runtime_error("boxmot_hip: stream " + std::to_string(s) + ": frame size changed (" + std::to_string(r0) + " x " + std::to_string(c0) +
+                                     " -> " + std::to_string(image_rows[s]) + " x " + std::to_string(image_cols[s]) + ")");
+    }
+    BM_HIP(hipStreamSynchronize(h->stream));
+    if (h->reid_stream) BM_HIP(hipStreamSynchronize(h->reid_stream));
+    h->fs_rows.assign(image_rows, image_rows + h->S);
+    h->fs_cols.assign(image_cols, image_cols + h->S);
+    h->fs_mixed = false;
+    std::vector<int> dims((size_t)h->S * 2);
+    for (int s = 0; s < h->S; ++s) {
+        dims[2 * s] = image_cols[s]; dims[2 * s + 1] = image_rows[s];
+        if (image_rows[s] != image_rows[0] || image_cols[s] != image_cols[0]) h->fs_mixed = true;
+    }
+    if (!h->d_fs_dims) h->d_fs_dims = dev_alloc<int>((size_t)h->S * 2, h->owned);
+    BM_HIP(hipMemcpy(h->d_fs_dims, dims.data(), dims.size() * sizeof(int), hipMemcpyHostToDevice));
+}
+
 // Validate and upload the inputs of the first n streams; run the ReID engine on every detection passing the confidence
 // test (`conf > thresh`, or `>=` when inclusive) when embeddings are wanted and not supplied.  Streams without a pending
 // warp get the identity.  Returns whether any stream has a pending warp.
@@ -1302,9 +1396,21 @@ bool io_stage(StreamIo* h, int n, const StreamIn* in, int det_cols, int emb_cols
     if (!h->reid) throw std::runtime_error("boxmot_hip: embeddings are needed and none were supplied, but no ReID weights are loaded");
     if (image_channels != 3) throw std::runtime_error("boxmot_hip: ReID needs a 3-channel uint8 BGR image");
     const size_t bytes = (size_t)image_rows * image_cols * 3;
+    const bool sized = !h->fs_rows.empty();
     for (int k = 0; k < n; ++k) {
         const int sk = s0 + k;
         if (!in[k].image) { if (!h->frame_bufs[sk]) throw std::runtime_error("Image data pointer is null."); continue; }
+        if (sized) {        // one buffer per stream of that stream's size (the scalar arguments are not used)
+            const size_t sbytes = (size_t)h->fs_rows[sk] * h->fs_cols[sk] * 3;
+            if (h->frame_bufs[sk] == nullptr) {
+                void* p = nullptr;
+                BM_HIP(hipMalloc(&p, sbytes));
+                h->frame_bufs[sk] = static_cast<uint8_t*>(p);
+                BM_HIP(hipMemcpy(h->d_frames, h->frame_bufs.data(), h->S * sizeof(uint8_t*), hipMemcpyHostToDevice));
+            }
+            BM_HIP(hipMemcpyAsync(h->frame_bufs[sk], in[k].image, sbytes, hipMemcpyHostToDevice, h->stream));
+            continue;
+        }
         if (h->frame_bufs[sk] == nullptr || bytes != h->frame_bytes) {
             if (h->frame_bytes != 0 && bytes != h->frame_bytes) throw std::runtime_error("boxmot_hip: frame size changed between updates");
             void* p = nullptr;
@@ -1316,6 +1422,8 @@ bool io_stage(StreamIo* h, int n, const StreamIn* in, int det_cols, int emb_cols
         BM_HIP(hipMemcpyAsync(h->frame_bufs[sk], in[k].image, bytes, hipMemcpyHostToDevice, h->stream));
     }
     h->engine_on_main = true;           // (a later pipelined step_device_frames orders its ReID pass after this use)
+    IoDimsScope dims_scope{h->reid.get()};
+    if (sized) { h->frame_rows = h->fs_rows[0]; h->frame_cols = h->fs_cols[0]; h->reid->set_frame_dims(h->fs_mixed ? h->d_fs_dims : nullptr); }
     BM_HIP(hipMemsetAsync(h->d_crop_count, 0, 4, h->stream));
     hipLaunchKernelGGL(build_crop_list_kernel, dim3(n), dim3(256), 0, h->stream, h->d_dets, h->d_ndets, nd, reid_thresh,
                        h->d_crop_count, h->d_crop_stream, h->d_crop_boxes, h->d_crop_row, s0, inclusive);
@@ -1338,7 +1446,10 @@ bool io_stage(StreamIo* h, int n, const StreamIn* in, int det_cols, int emb_cols
 float* io_device_reid(StreamIo* h, const float* d_dets, const int* d_ndets, const uint8_t* const* d_frames, int image_rows,
                       int image_cols, double reid_thresh, int inclusive) {
     if (!h->reid) throw std::runtime_error("boxmot_hip: embeddings are needed and none were supplied, but no ReID weights are loaded");
-    if (!d_frames || image_rows <= 0 || image_cols <= 0) throw std::runtime_error("boxmot_hip: step_device_frames needs device frames");
+    const bool sized = !h->fs_rows.empty();
+    if (!d_frames || (!sized && (image_rows <= 0 || image_cols <= 0))) throw std::runtime_error("boxmot_hip: step_device_frames needs device frames");
+    IoDimsScope dims_scope{h->reid.get()};
+    if (sized) { image_rows = h->fs_rows[0]; image_cols = h->fs_cols[0]; h->reid->set_frame_dims(h->fs_mixed ? h->d_fs_dims : nullptr); }
     // pipeline stage 1 (StreamIo): this frame's ReID on `reid_stream`, into the table the step before last has finished reading
     const bool pipe = h->pipe && h->reid_stream;
     hipStream_t rs = pipe ? h->reid_stream : h->stream;
@@ -1812,11 +1923,42 @@ int boxmot_hip_botsort_update_batch_frames(BoxMOTHipBotSort* handle, int n_strea
         if (!handle) throw std::runtime_error("boxmot_hip BoT-SORT handle is not initialized.");
         if (n_streams < 1 || n_streams > handle->S) throw std::runtime_error("boxmot_hip: n_streams out of range");
         if (!dets || !det_rows || !out_tracks || !out_rows) throw std::runtime_error("boxmot_hip: null batch pointers");
-        if (!d_frames || image_rows < 1 || image_cols < 1) throw std::runtime_error("boxmot_hip: update_batch_frames needs device frames");
+        if (!d_frames || (handle->fs_rows.empty() && (image_rows < 1 || image_cols < 1))) throw std::runtime_error("boxmot_hip: update_batch_frames needs device frames");
         std::vector<StreamIn> in(n_streams);
         for (int s = 0; s < n_streams; ++s) in[s] = StreamIn{dets[s], det_rows[s], (embs && emb_cols > 0) ? embs[s] : nullptr, nullptr};
         host_update(handle, 0, n_streams, in.data(), handle->det_cols(), emb_cols, image_rows, image_cols, 3, nullptr, nullptr, out_tracks,
                     out_capacity_rows, out_rows, d_frames);
+    });
+}
+
+int boxmot_hip_botsort_set_frame_sizes(BoxMOTHipBotSort* handle, const int* image_rows, const int* image_cols, int n_streams) {
+    return guard_on(handle, [&]() {
+        if (!handle || !image_rows || !image_cols) throw std::runtime_error("boxmot_hip: null argument");
+        BoxMOTHipBotSort* h = handle;
+        if (n_streams != h->S) throw std::runtime_error("boxmot_hip: set_frame_sizes needs one (rows, cols) per stream of the handle (" + std::to_string(h->S) + ")");
+        for (int s = 0; s < h->S; ++s) {
+            if (image_rows[s] < 1 || image_cols[s] < 1) throw std::runtime_error("boxmot_hip: stream " + std::to_string(s) + ": frame dimensions must be positive");
+            // a stream's size is fixed by its first frame (or an earlier declaration)
+            const bool seen = h->frame_bufs[s] != nullptr || !h->fs_rows.empty();
+            const int r0 = h->fs_rows.empty() ? h->frame_rows : h->fs_rows[s], c0 = h->fs_cols.empty() ? h->frame_cols : h->fs_cols[s];
+            if (seen && (r0 != image_rows[s] || c0 != image_cols[s]))
+                throw std::runtime_error("boxmot_hip: stream " + std::to_string(s) + ": frame size changed (" + std::to_string(r0) + " x " + std::to_string(c0) +
+                                         " -> " + std::to_string(image_rows[s]) + " x " + std::to_string(image_cols[s]) + ")");
+        }
+        if ((h->sof || h->ecc) && h->fs_rows.empty())
+            throw std::runtime_error("boxmot_hip: set_frame_sizes comes before the first update of a handle that estimates camera motion itself");
+        BM_HIP(hipStreamSynchronize(h->stream));
+        if (h->reid_stream) BM_HIP(hipStreamSynchronize(h->reid_stream));
+        h->fs_rows.assign(image_rows, image_rows + h->S);
+        h->fs_cols.assign(image_cols, image_cols + h->S);
+        h->fs_mixed = false;
+        std::vector<int> dims((size_t)h->S * 2);
+        for (int s = 0; s < h->S; ++s) {
+            dims[2 * s] = image_cols[s]; dims[2 * s + 1] = image_rows[s];
+            if (image_rows[s] != image_rows[0] || image_cols[s] != image_cols[0]) h->fs_mixed = true;
+        }
+        if (!h->d_fs_dims) h->d_fs_dims = dev_alloc<int>((size_t)h->S * 2, h->owned);
+        BM_HIP(hipMemcpy(h->d_fs_dims, dims.data(), dims.size() * sizeof(int), hipMemcpyHostToDevice));
     });
 }
 
@@ -1859,23 +2001,16 @@ int boxmot_hip_botsort_step_device(BoxMOTHipBotSort* handle, const float* d_dets
             bool missing = false;
             for (int s = 0; s < h->S; ++s) missing = missing || h->h_warp_flag[s] == 0;
             if (missing) {
-                if (!d_frames || image_rows < 1 || image_cols < 1)
+                if (!d_frames || (h->fs_rows.empty() && (image_rows < 1 || image_cols < 1)))
                     throw std::runtime_error("boxmot_hip: cmc_method=sof/ecc in a device-resident step needs d_frames (or a warp per stream from set_warp)");
-                if (h->use_sof) {
-                    if (!h->sof) { h->sof.reset(new BoxMOTHipSof()); sof_init(h->sof.get(), h->S, image_rows, image_cols, 0.15, 8, 0.2, 3.0, h->stream); }
-                    if (h->sof->rows != image_rows || h->sof->cols != image_cols) throw std::runtime_error("boxmot_hip: frame size changed between updates");
-                } else {
-                    if (!h->ecc) { h->ecc.reset(new BoxMOTHipEcc()); ecc_init(h->ecc.get(), h->S, image_rows, image_cols, 0.15, 1e-5, 100, h->stream); }
-                    if (h->ecc->rows != image_rows || h->ecc->cols != image_cols) throw std::runtime_error("boxmot_hip: frame size changed between updates");
-                }
                 std::vector<double> w(6);
                 for (int s = 0; s < h->S; ++s) {
                     if (h->h_warp_flag[s]) continue;
                     if (h->use_sof && h->is_obb) {
                         hipLaunchKernelGGL(obb_enclosing_boxes_kernel, dim3(1), dim3(256), 0, h->stream, d_dets, d_det_rows, h->nd, h->d_cmc_boxes, s);
-                        sof_run(h->sof.get(), s, 1, d_frames + s, h->d_cmc_boxes + (size_t)s * h->nd * 4, d_det_rows + s, h->nd, 4, w.data(), nullptr);
-                    } else if (h->use_sof) sof_run(h->sof.get(), s, 1, d_frames + s, d_dets + (size_t)s * h->nd * bm::DET_COLS, d_det_rows + s, h->nd, bm::DET_COLS, w.data(), nullptr);
-                    else ecc_run_one(h->ecc.get(), s, d_frames + s, w.data(), nullptr);
+                        sof_run(sof_of(h, s, image_rows, image_cols), s, 1, d_frames + s, h->d_cmc_boxes + (size_t)s * h->nd * 4, d_det_rows + s, h->nd, 4, w.data(), nullptr);
+                    } else if (h->use_sof) sof_run(sof_of(h, s, image_rows, image_cols), s, 1, d_frames + s, d_dets + (size_t)s * h->nd * bm::DET_COLS, d_det_rows + s, h->nd, bm::DET_COLS, w.data(), nullptr);
+                    else ecc_run_one(ecc_of(h, s, image_rows, image_cols), s, d_frames + s, w.data(), nullptr);
                     for (int k = 0; k < 6; ++k) h->h_warp[(size_t)s * 6 + k] = w[k];
                     h->h_warp_flag[s] = 1;
                 }
@@ -2126,29 +2261,14 @@ int boxmot_hip_reid_set_mode(BoxMOTHipReID* handle, int mode) {
     });
 }
 
-static void reid_stage(BoxMOTHipReID* h, const uint8_t* image, int rows, int cols, int channels, const float* boxes,
-                       int n, int box_cols) {
-    if (!h) throw std::runtime_error("boxmot_hip: null ReID handle");
-    if (!image) throw std::runtime_error("Image data pointer is null.");
-    if (channels != 3) throw std::runtime_error("boxmot_hip: ReID needs a 3-channel uint8 BGR image");
-    if (rows <= 0 || cols <= 0) throw std::runtime_error("Image dimensions must be positive.");
-    if (n < 0 || box_cols < 4) throw std::runtime_error("boxmot_hip: boxes must have at least 4 columns");
-    if (n > h->engine->max_crops()) throw std::runtime_error("boxmot_hip: more boxes than max_crops");
-    const size_t bytes = (size_t)rows * cols * 3;
-    if (bytes > h->frame_bytes) {
-        if (h->d_frame) BM_HIP(hipFree(h->d_frame));
-        void* p = nullptr;
-        BM_HIP(hipMalloc(&p, bytes));
-        h->d_frame = static_cast<uint8_t*>(p);
-        h->frame_bytes = bytes;
-        BM_HIP(hipMemcpy(h->d_frames, &h->d_frame, sizeof(uint8_t*), hipMemcpyHostToDevice));
-    }
-    BM_HIP(hipMemcpyAsync(h->d_frame, image, bytes, hipMemcpyHostToDevice, h->stream));
-    // base_backend.py:119-122, 157: rows of 5 / 7 / 9 values are oriented boxes [cx, cy, w, h, angle, ...]
-    h->obb = n > 0 && (box_cols == 5 || box_cols == 7 || box_cols == 9);
-    std::vector<float> b((size_t)n * 4);
-    std::vector<double> geo;
-    if (h->obb) {
+// Host side of the box table: xyxy rows copied to 4 columns, or -- rows of 5 / 7 / 9 values (base_backend.py:119-122, 157) -- the
+// geometry of oriented boxes [cx, cy, w, h, angle, ...] (8 doubles per box: out_w, out_h, inverse 2x3 map).  Returns whether the
+// boxes are oriented.
+static bool reid_host_boxes(const float* boxes, int n, int box_cols, std::vector<float>& b, std::vector<double>& geo) {
+    const bool obb = n > 0 && (box_cols == 5 || box_cols == 7 || box_cols == 9);
+    b.assign((size_t)n * 4, 0.f);
+    geo.clear();
+    if (obb) {
         // _crop_obb (base_backend.py:91-117): getRotationMatrix2D about the box centre, shifted so that the centre lands on the middle
         // of the (round(w), round(h)) output; cv2.warpAffine inverts the matrix in double precision before it samples
         geo.resize((size_t)n * 8);
@@ -2171,13 +2291,36 @@ static void reid_stage(BoxMOTHipReID* h, const uint8_t* image, int rows, int col
             g[2] = A11; g[3] = m01 * (-D); g[5] = m10 * (-D); g[6] = A22;
             g[4] = -g[2] * m02 - g[3] * m12;
             g[7] = -g[5] * m02 - g[6] * m12;
-            for (int q = 0; q < 4; ++q) b[i * 4 + q] = 0.f;
         }
-        BM_HIP(hipMemcpyAsync(h->d_obb, geo.data(), geo.size() * 8, hipMemcpyHostToDevice, h->stream));
     } else {
         for (int i = 0; i < n; ++i)
             for (int q = 0; q < 4; ++q) b[i * 4 + q] = boxes[(size_t)i * box_cols + q];
     }
+    return obb;
+}
+
+static void reid_stage(BoxMOTHipReID* h, const uint8_t* image, int rows, int cols, int channels, const float* boxes,
+                       int n, int box_cols) {
+    if (!h) throw std::runtime_error("boxmot_hip: null ReID handle");
+    if (!image) throw std::runtime_error("Image data pointer is null.");
+    if (channels != 3) throw std::runtime_error("boxmot_hip: ReID needs a 3-channel uint8 BGR image");
+    if (rows <= 0 || cols <= 0) throw std::runtime_error("Image dimensions must be positive.");
+    if (n < 0 || box_cols < 4) throw std::runtime_error("boxmot_hip: boxes must have at least 4 columns");
+    if (n > h->engine->max_crops()) throw std::runtime_error("boxmot_hip: more boxes than max_crops");
+    const size_t bytes = (size_t)rows * cols * 3;
+    if (bytes > h->frame_bytes) {
+        if (h->d_frame) BM_HIP(hipFree(h->d_frame));
+        void* p = nullptr;
+        BM_HIP(hipMalloc(&p, bytes));
+        h->d_frame = static_cast<uint8_t*>(p);
+        h->frame_bytes = bytes;
+        BM_HIP(hipMemcpy(h->d_frames, &h->d_frame, sizeof(uint8_t*), hipMemcpyHostToDevice));
+    }
+    BM_HIP(hipMemcpyAsync(h->d_frame, image, bytes, hipMemcpyHostToDevice, h->stream));
+    std::vector<float> b;
+    std::vector<double> geo;
+    h->obb = reid_host_boxes(boxes, n, box_cols, b, geo);
+    if (h->obb) BM_HIP(hipMemcpyAsync(h->d_obb, geo.data(), geo.size() * 8, hipMemcpyHostToDevice, h->stream));
     if (n) BM_HIP(hipMemcpyAsync(h->d_boxes, b.data(), b.size() * 4, hipMemcpyHostToDevice, h->stream));
     BM_HIP(hipStreamSynchronize(h->stream));
     h->engine->set_obb_geometry(h->obb ? h->d_obb : nullptr);
@@ -2201,6 +2344,123 @@ int boxmot_hip_reid_compute_features(BoxMOTHipReID* handle, const uint8_t* image
                             handle->d_feat, nullptr, handle->stream);
         BM_HIP(hipMemcpyAsync(out_features, handle->d_feat, (size_t)n_boxes * handle->engine->feature_dim() * 4,
                               hipMemcpyDeviceToHost, handle->stream));
+        BM_HIP(hipStreamSynchronize(handle->stream));
+    });
+}
+
+// ---- boxes of many images, of any sizes, in one device pass ----
+// the per-image frame sizes are valid for one batch call only
+struct DimsScope {
+    BoxMOTHipReID* h;
+    ~DimsScope() { if (h && h->engine) { h->engine->set_frame_dims(nullptr); h->engine->set_obb_geometry(nullptr); } }
+};
+
+// Validate, upload the images, bring the pointer and {W, H} tables up to date.  Returns whether the images differ in size (the
+// engine then reads the table; with one size the scalar-form kernels run, as for a single image).
+static bool reid_stage_images(BoxMOTHipReID* h, const uint8_t* const* images, const int* rows, const int* cols, int n_images,
+                              const int* box_image, int n_boxes, int box_cols) {
+    if (!h) throw std::runtime_error("boxmot_hip: null ReID handle");
+    if (!images || !rows || !cols || n_images < 1) throw std::runtime_error("boxmot_hip: ReID batch needs at least one image and its size");
+    if (n_boxes < 0 || box_cols < 4) throw std::runtime_error("boxmot_hip: boxes must have at least 4 columns");
+    if (n_boxes > 0 && !box_image) throw std::runtime_error("boxmot_hip: ReID batch needs the image index of every box");
+    for (int k = 0; k < n_images; ++k) {
+        if (!images[k]) throw std::runtime_error("boxmot_hip: ReID batch image " + std::to_string(k) + ": data pointer is null");
+        if (rows[k] <= 0 || cols[k] <= 0) throw std::runtime_error("boxmot_hip: ReID batch image " + std::to_string(k) + ": dimensions must be positive");
+    }
+    for (int i = 0; i < n_boxes; ++i)
+        if (box_image[i] < 0 || box_image[i] >= n_images)
+            throw std::runtime_error("boxmot_hip: ReID batch box " + std::to_string(i) + ": image index out of range");
+    bool tables_stale = false;
+    if ((int)h->batch_bufs.size() < n_images) {
+        BM_HIP(hipStreamSynchronize(h->stream));
+        if (h->d_batch_frames) BM_HIP(hipFree(h->d_batch_frames));
+        if (h->d_batch_dims) BM_HIP(hipFree(h->d_batch_dims));
+        h->d_batch_frames = nullptr; h->d_batch_dims = nullptr;
+        void* p = nullptr;
+        BM_HIP(hipMalloc(&p, (size_t)n_images * sizeof(uint8_t*)));
+        h->d_batch_frames = static_cast<const uint8_t**>(p);
+        BM_HIP(hipMalloc(&p, (size_t)n_images * 2 * sizeof(int)));
+        h->d_batch_dims = static_cast<int*>(p);
+        h->batch_bufs.resize(n_images, nullptr);
+        h->batch_bytes.resize(n_images, 0);
+        h->batch_dims.resize((size_t)n_images * 2, 0);
+        tables_stale = true;
+    }
+    bool mixed = false;
+    for (int k = 0; k < n_images; ++k) {
+        const size_t bytes = (size_t)rows[k] * cols[k] * 3;
+        if (bytes > h->batch_bytes[k]) {
+            if (h->batch_bufs[k]) { BM_HIP(hipFree(h->batch_bufs[k])); h->batch_bufs[k] = nullptr; h->batch_bytes[k] = 0; }
+            void* p = nullptr;
+            BM_HIP(hipMalloc(&p, bytes));
+            h->batch_bufs[k] = static_cast<uint8_t*>(p);
+            h->batch_bytes[k] = bytes;
+            tables_stale = true;
+        }
+        if (h->batch_dims[2 * k] != cols[k] || h->batch_dims[2 * k + 1] != rows[k]) {
+            h->batch_dims[2 * k] = cols[k]; h->batch_dims[2 * k + 1] = rows[k];
+            tables_stale = true;
+        }
+        if (rows[k] != rows[0] || cols[k] != cols[0]) mixed = true;
+        BM_HIP(hipMemcpyAsync(h->batch_bufs[k], images[k], bytes, hipMemcpyHostToDevice, h->stream));
+    }
+    if (tables_stale) {     // sizes are a property of the caller's streams: the tables change when one of them does, not per call
+        BM_HIP(hipMemcpyAsync(h->d_batch_frames, h->batch_bufs.data(), h->batch_bufs.size() * sizeof(uint8_t*), hipMemcpyHostToDevice, h->stream));
+        BM_HIP(hipMemcpyAsync(h->d_batch_dims, h->batch_dims.data(), h->batch_dims.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        BM_HIP(hipStreamSynchronize(h->stream));       // (the copies read pageable vectors of the handle)
+    }
+    if (!h->d_batch_crop_stream) h->d_batch_crop_stream = zalloc<int>(h->engine->max_crops(), h->owned);
+    return mixed;
+}
+
+// boxes [i0, i0 + m) of the batch -> the handle's device tables (boxes, oriented geometry, crop -> image)
+static void reid_stage_box_chunk(BoxMOTHipReID* h, const float* boxes, const int* box_image, int i0, int m, int box_cols) {
+    std::vector<float> b;
+    std::vector<double> geo;
+    h->obb = reid_host_boxes(boxes + (size_t)i0 * box_cols, m, box_cols, b, geo);
+    if (h->obb) BM_HIP(hipMemcpyAsync(h->d_obb, geo.data(), geo.size() * 8, hipMemcpyHostToDevice, h->stream));
+    BM_HIP(hipMemcpyAsync(h->d_boxes, b.data(), b.size() * 4, hipMemcpyHostToDevice, h->stream));
+    BM_HIP(hipMemcpyAsync(h->d_batch_crop_stream, box_image + i0, (size_t)m * 4, hipMemcpyHostToDevice, h->stream));
+    BM_HIP(hipStreamSynchronize(h->stream));
+    h->engine->set_obb_geometry(h->obb ? h->d_obb : nullptr);
+}
+
+int boxmot_hip_reid_compute_features_batch(BoxMOTHipReID* handle, const uint8_t* const* images, const int* image_rows,
+                                           const int* image_cols, int n_images, const float* boxes, const int* box_image, int n_boxes,
+                                           int box_cols, float* out_features, int out_capacity_rows) {
+    return guard_on(handle, [&]() {
+        DimsScope scope{handle};
+        const bool mixed = reid_stage_images(handle, images, image_rows, image_cols, n_images, box_image, n_boxes, box_cols);
+        if (out_capacity_rows < n_boxes) throw std::runtime_error("boxmot_hip: feature buffer too small");
+        if (n_boxes > 0 && !out_features) throw std::runtime_error("boxmot_hip: null argument");
+        if (n_boxes == 0) { BM_HIP(hipStreamSynchronize(handle->stream)); return; }     // (the uploads read the caller's memory: done before returning)
+        handle->engine->set_frame_dims(mixed ? handle->d_batch_dims : nullptr);
+        const int step = handle->engine->max_crops(), dim = handle->engine->feature_dim();
+        for (int i0 = 0; i0 < n_boxes; i0 += step) {         // the handle's box / feature tables hold max_crops rows
+            const int m = n_boxes - i0 < step ? n_boxes - i0 : step;
+            reid_stage_box_chunk(handle, boxes, box_image, i0, m, box_cols);
+            handle->engine->run(handle->d_batch_frames, handle->d_batch_crop_stream, handle->d_boxes, 4, m, image_cols[0], image_rows[0],
+                                handle->d_feat, nullptr, handle->stream);
+            BM_HIP(hipMemcpyAsync(out_features + (size_t)i0 * dim, handle->d_feat, (size_t)m * dim * 4, hipMemcpyDeviceToHost, handle->stream));
+            BM_HIP(hipStreamSynchronize(handle->stream));
+        }
+    });
+}
+
+int boxmot_hip_reid_preprocess_batch(BoxMOTHipReID* handle, const uint8_t* const* images, const int* image_rows, const int* image_cols,
+                                     int n_images, const float* boxes, const int* box_image, int n_boxes, int box_cols, float* out_crops) {
+    return guard_on(handle, [&]() {
+        DimsScope scope{handle};
+        const bool mixed = reid_stage_images(handle, images, image_rows, image_cols, n_images, box_image, n_boxes, box_cols);
+        if (n_boxes > handle->engine->max_crops()) throw std::runtime_error("boxmot_hip: more boxes than max_crops");
+        if (n_boxes == 0) { BM_HIP(hipStreamSynchronize(handle->stream)); return; }
+        if (!out_crops) throw std::runtime_error("boxmot_hip: null argument");
+        handle->engine->set_frame_dims(mixed ? handle->d_batch_dims : nullptr);
+        reid_stage_box_chunk(handle, boxes, box_image, 0, n_boxes, box_cols);
+        handle->engine->preprocess_fp32(handle->d_batch_frames, handle->d_batch_crop_stream, handle->d_boxes, 4, n_boxes, image_cols[0],
+                                        image_rows[0], handle->stream);
+        BM_HIP(hipMemcpyAsync(out_crops, handle->engine->crops_buffer(),
+                              (size_t)n_boxes * bm::REID_IN_H * bm::REID_IN_W * 3 * 4, hipMemcpyDeviceToHost, handle->stream));
         BM_HIP(hipStreamSynchronize(handle->stream));
     });
 }
@@ -2371,6 +2631,30 @@ int boxmot_hip_sof_debug_map(BoxMOTHipSof* handle, int stream, int which, void* 
 }
 
 // ---- frame ingest ring ----
+// slots of a ring whose per-stream offsets (h->offs) are set: pinned host frames, device twins, pointer tables, events
+static void ingest_build(BoxMOTHipIngest* h) {
+    const int n_slots = h->n_slots, n_streams = h->n_streams;
+    BM_HIP(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
+    const size_t slot_bytes = h->offs[n_streams];
+    for (int k = 0; k < n_slots; ++k) {
+        void *hp = nullptr, *dp = nullptr, *tp = nullptr;
+        BM_HIP(hipHostMalloc(&hp, slot_bytes, hipHostMallocDefault));
+        h->h_slot.push_back(static_cast<uint8_t*>(hp));
+        BM_HIP(hipMalloc(&dp, slot_bytes));
+        h->d_slot.push_back(static_cast<uint8_t*>(dp));
+        BM_HIP(hipMalloc(&tp, n_streams * sizeof(uint8_t*)));
+        h->d_ptrs.push_back(static_cast<const uint8_t**>(tp));
+        std::vector<const uint8_t*> table(n_streams);
+        for (int s = 0; s < n_streams; ++s) table[s] = h->d_slot[k] + h->offs[s];
+        BM_HIP(hipMemcpy(tp, table.data(), n_streams * sizeof(uint8_t*), hipMemcpyHostToDevice));
+        hipEvent_t a, b;
+        BM_HIP(hipEventCreateWithFlags(&a, hipEventDisableTiming));
+        BM_HIP(hipEventCreateWithFlags(&b, hipEventDisableTiming));
+        h->uploaded.push_back(a); h->consumed.push_back(b);
+    }
+    h->has_consumer.assign(n_slots, 0);
+}
+
 BoxMOTHipIngest* boxmot_hip_ingest_create(int n_slots, int n_streams, int image_rows, int image_cols) {
     BoxMOTHipIngest* h = nullptr;
     const int ok = guard([&]() {
@@ -2380,25 +2664,32 @@ BoxMOTHipIngest* boxmot_hip_ingest_create(int n_slots, int n_streams, int image_
         h = new BoxMOTHipIngest();
         h->n_slots = n_slots; h->n_streams = n_streams; h->rows = image_rows; h->cols = image_cols;
         h->frame_bytes = (size_t)image_rows * image_cols * 3;
-        BM_HIP(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-        const size_t slot_bytes = h->frame_bytes * n_streams;
-        for (int k = 0; k < n_slots; ++k) {
-            void *hp = nullptr, *dp = nullptr, *tp = nullptr;
-            BM_HIP(hipHostMalloc(&hp, slot_bytes, hipHostMallocDefault));
-            h->h_slot.push_back(static_cast<uint8_t*>(hp));
-            BM_HIP(hipMalloc(&dp, slot_bytes));
-            h->d_slot.push_back(static_cast<uint8_t*>(dp));
-            BM_HIP(hipMalloc(&tp, n_streams * sizeof(uint8_t*)));
-            h->d_ptrs.push_back(static_cast<const uint8_t**>(tp));
-            std::vector<const uint8_t*> table(n_streams);
-            for (int s = 0; s < n_streams; ++s) table[s] = h->d_slot[k] + (size_t)s * h->frame_bytes;
-            BM_HIP(hipMemcpy(tp, table.data(), n_streams * sizeof(uint8_t*), hipMemcpyHostToDevice));
-            hipEvent_t a, b;
-            BM_HIP(hipEventCreateWithFlags(&a, hipEventDisableTiming));
-            BM_HIP(hipEventCreateWithFlags(&b, hipEventDisableTiming));
-            h->uploaded.push_back(a); h->consumed.push_back(b);
-        }
-        h->has_consumer.assign(n_slots, 0);
+        h->offs.resize((size_t)n_streams + 1);
+        for (int s = 0; s <= n_streams; ++s) h->offs[s] = (size_t)s * h->frame_bytes;
+        ingest_build(h);
+    });
+    if (!ok) { delete h; return nullptr; }
+    return h;
+}
+
+// a ring whose streams have frames of different sizes: stream s is (image_rows[s], image_cols[s], 3); the frames of a slot lie in one
+// allocation at 256-byte aligned offsets, so submit stays one DMA per slot
+BoxMOTHipIngest* boxmot_hip_ingest_create_sized(int n_slots, int n_streams, const int* image_rows, const int* image_cols) {
+    BoxMOTHipIngest* h = nullptr;
+    const int ok = guard([&]() {
+        require_device();
+        if (n_slots < 2 || n_streams < 1 || !image_rows || !image_cols)
+            throw std::runtime_error("boxmot_hip: ingest ring needs >= 2 slots, >= 1 stream and a (rows, cols) per stream");
+        for (int s = 0; s < n_streams; ++s)
+            if (image_rows[s] < 1 || image_cols[s] < 1)
+                throw std::runtime_error("boxmot_hip: ingest ring stream " + std::to_string(s) + ": frame dimensions must be positive");
+        h = new BoxMOTHipIngest();
+        h->n_slots = n_slots; h->n_streams = n_streams; h->rows = image_rows[0]; h->cols = image_cols[0];
+        h->frame_bytes = 0;             // (no single frame size)
+        h->offs.assign((size_t)n_streams + 1, 0);
+        for (int s = 0; s < n_streams; ++s)
+            h->offs[s + 1] = (h->offs[s] + (size_t)image_rows[s] * image_cols[s] * 3 + 255) / 256 * 256;
+        ingest_build(h);
     });
     if (!ok) { delete h; return nullptr; }
     return h;
@@ -2416,7 +2707,7 @@ uint8_t* boxmot_hip_ingest_host_ptr(BoxMOTHipIngest* handle, int slot, int strea
     guard_on(handle, [&]() {
         ingest_slot(handle, slot);
         if (stream < 0 || stream >= handle->n_streams) throw std::runtime_error("boxmot_hip: stream index out of range");
-        p = handle->h_slot[slot] + (size_t)stream * handle->frame_bytes;
+        p = handle->h_slot[slot] + handle->offs[stream];
     });
     return p;
 }
@@ -2433,7 +2724,7 @@ int boxmot_hip_ingest_submit(BoxMOTHipIngest* handle, int slot, int n_streams) {
         if (n_streams < 1 || n_streams > handle->n_streams) throw std::runtime_error("boxmot_hip: stream count out of range");
         // the previous consumer of this slot must be done with the device frames before they are overwritten
         if (handle->has_consumer[slot]) BM_HIP(hipStreamWaitEvent(handle->copy_stream, handle->consumed[slot], 0));
-        BM_HIP(hipMemcpyAsync(handle->d_slot[slot], handle->h_slot[slot], handle->frame_bytes * n_streams, hipMemcpyHostToDevice,
+        BM_HIP(hipMemcpyAsync(handle->d_slot[slot], handle->h_slot[slot], handle->offs[n_streams], hipMemcpyHostToDevice,
                               handle->copy_stream));
         BM_HIP(hipEventRecord(handle->uploaded[slot], handle->copy_stream));
     });
@@ -2616,6 +2907,21 @@ int boxmot_hip_deepocsort_step_device_frames(BoxMOTHipDeepOcSort* handle, const 
         BM_HIP(hipGetLastError());
         if (embs) io_pipe_step_enqueued(handle);
         io_clear_warps(handle);
+    });
+}
+
+int boxmot_hip_deepocsort_set_frame_sizes(BoxMOTHipDeepOcSort* handle, const int* image_rows, const int* image_cols, int n_streams) {
+    return guard_on(handle, [&]() {
+        if (!handle) throw std::runtime_error("boxmot_hip DeepOCSORT handle is not initialized.");
+        // asso_func centroid normalises by the frame diagonal, ONE number per handle inside the step (docs_set_frame_size): it is
+        // refused on a handle whose streams differ in size, not approximated
+        if (handle->args.cfg.asso_mode == BOXMOT_HIP_ASSO_CENTROID && image_rows && image_cols && n_streams == handle->S)
+            for (int s = 1; s < n_streams; ++s)
+                if (image_rows[s] != image_rows[0] || image_cols[s] != image_cols[0])
+                    throw std::runtime_error("boxmot_hip: asso_func centroid normalises by one frame diagonal per handle: streams of different "
+                                             "frame sizes (stream " + std::to_string(s) + " differs from stream 0) need another asso_func or one handle per size");
+        io_set_frame_sizes(handle, image_rows, image_cols, n_streams);
+        docs_need_frame_size(handle, image_rows[0], image_cols[0]);       // (one size: centroid takes it, if the config gave none)
     });
 }
 
@@ -2806,6 +3112,13 @@ int boxmot_hip_strongsort_step_device_frames(BoxMOTHipStrongSort* handle, const 
         BM_HIP(hipGetLastError());
         io_pipe_step_enqueued(handle);
         io_clear_warps(handle);
+    });
+}
+
+int boxmot_hip_strongsort_set_frame_sizes(BoxMOTHipStrongSort* handle, const int* image_rows, const int* image_cols, int n_streams) {
+    return guard_on(handle, [&]() {
+        if (!handle) throw std::runtime_error("boxmot_hip StrongSORT handle is not initialized.");
+        io_set_frame_sizes(handle, image_rows, image_cols, n_streams);
     });
 }
 

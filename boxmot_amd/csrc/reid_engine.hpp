@@ -159,6 +159,10 @@ public:
     // oriented boxes for the next preprocess / run: device array [n][8] doubles (out_w, out_h, inverse 2x3 map) or nullptr (axis-aligned).
     // In a chunked run the caller passes the chunk's slice (run() processes boxes from index 0 of what it is given).
     void set_obb_geometry(const double* d_geo) { obb_geo_ = d_geo; }
+    // per-stream frame sizes for the following preprocess / run / run_counted calls: device table of {W, H} int pairs indexed by
+    // stream (what d_crop_stream holds), or nullptr -- every stream has the size given by the scalar W, H arguments.  With a table
+    // the `_sized` kernels run and W, H are not used; without one the launches are exactly the scalar-form ones.
+    void set_frame_dims(const int* d_dims) { dims_ = d_dims; }
     int preprocess_mode() const { return pad_; }
     const OsnetLayout& layout() const { return L_; }
     float* crops_buffer() { return crops_; }
@@ -172,6 +176,11 @@ public:
             if (n > (whp ? wide_hp_->max_crops() : fused_cap_)) throw std::runtime_error("ReID: crop batch exceeds the engine capacity");
             if (n == 0) return;
             if (obb_geo_) throw std::runtime_error("ReID mode 2 (fused fp32-grade kernels): oriented-box crops run in modes 0 / 1");
+            if (dims_)
+                hipLaunchKernelGGL(k_crop_resize_rgbx_hl_sized, dim3(n, REID_IN_H / 16), dim3(REID_IN_W), 0, st, d_frames, d_crop_stream, d_boxes,
+                                   box_stride, dims_, d_lut_, whp ? wide_hp_->crops_h() : crops_h_, whp ? wide_hp_->crops_l() : crops_l_, 16,
+                                   whp ? static_cast<const int*>(nullptr) : d_count_, pad_);
+            else
             hipLaunchKernelGGL(k_crop_resize_rgbx_hl, dim3(n, REID_IN_H / 16), dim3(REID_IN_W), 0, st, d_frames, d_crop_stream, d_boxes,
                                box_stride, W, H, d_lut_, whp ? wide_hp_->crops_h() : crops_h_, whp ? wide_hp_->crops_l() : crops_l_, 16,
                                whp ? static_cast<const int*>(nullptr) : d_count_, pad_);
@@ -184,9 +193,25 @@ public:
         const int rows_per_block = 16;
         if (obb_geo_) {         // oriented boxes: the rectified crop is sampled on demand (k_crop_resize_obb), same output layouts
             const dim3 grid(n, REID_IN_H / rows_per_block), block(REID_IN_W);
+            if (dims_) {
+                if (wide) hipLaunchKernelGGL((k_crop_resize_obb_sized<_Float16, true>), grid, block, 0, st, d_frames, d_crop_stream, obb_geo_, dims_, d_lut_, wide_->crops_buffer(), rows_per_block, pad_);
+                else if (fused) hipLaunchKernelGGL((k_crop_resize_obb_sized<_Float16, true>), grid, block, 0, st, d_frames, d_crop_stream, obb_geo_, dims_, d_lut_, crops_h_, rows_per_block, pad_);
+                else hipLaunchKernelGGL((k_crop_resize_obb_sized<float, false>), grid, block, 0, st, d_frames, d_crop_stream, obb_geo_, dims_, d_lut_, crops_, rows_per_block, pad_);
+                return;
+            }
             if (wide) hipLaunchKernelGGL((k_crop_resize_obb<_Float16, true>), grid, block, 0, st, d_frames, d_crop_stream, obb_geo_, W, H, d_lut_, wide_->crops_buffer(), rows_per_block, pad_);
             else if (fused) hipLaunchKernelGGL((k_crop_resize_obb<_Float16, true>), grid, block, 0, st, d_frames, d_crop_stream, obb_geo_, W, H, d_lut_, crops_h_, rows_per_block, pad_);
             else hipLaunchKernelGGL((k_crop_resize_obb<float, false>), grid, block, 0, st, d_frames, d_crop_stream, obb_geo_, W, H, d_lut_, crops_, rows_per_block, pad_);
+            return;
+        }
+        if (dims_) {
+            const dim3 grid(n, REID_IN_H / rows_per_block), block(REID_IN_W);
+            if (wide) hipLaunchKernelGGL(k_crop_resize_rgbx_sized, grid, block, 0, st, d_frames, d_crop_stream, d_boxes, box_stride, dims_, d_lut_,
+                                         wide_->crops_buffer(), rows_per_block, static_cast<const int*>(nullptr), pad_);
+            else if (fused) hipLaunchKernelGGL(k_crop_resize_rgbx_sized, grid, block, 0, st, d_frames, d_crop_stream, d_boxes, box_stride, dims_, d_lut_,
+                                               crops_h_, rows_per_block, d_count_, pad_);
+            else hipLaunchKernelGGL(k_crop_resize_sized<float>, grid, block, 0, st, d_frames, d_crop_stream, d_boxes, box_stride, dims_, d_lut_,
+                                    crops_, rows_per_block, pad_);
             return;
         }
         if (wide)
@@ -232,7 +257,7 @@ public:
             else if (wide) wide_->forward(m, o, orow, st);
             else if (wide_hp) wide_hp_->forward(m, o, orow, st);
             else if (mode_ >= 1) {
-                const FrameArgs fa{d_frames, d_crop_stream + i0, d_boxes + (long)i0 * box_stride, box_stride, W, H};
+                const FrameArgs fa{d_frames, d_crop_stream + i0, d_boxes + (long)i0 * box_stride, box_stride, W, H, dims_};
                 if (mode_ == 2) forward_hp(m, fuse_stem ? &fa : nullptr, o, orow, st);
                 else forward_fused(m, fuse_stem ? &fa : nullptr, o, orow, st);
             } else forward_v1(m, o, orow, st);
@@ -258,7 +283,7 @@ public:
         BM_HIP(hipEventRecord(ev_[1], st));
         hipEvent_t a = take_event(), b = take_event();
         BM_HIP(hipEventRecord(a, st));
-        const FrameArgs fa{d_frames, d_crop_stream, d_boxes, box_stride, W, H};
+        const FrameArgs fa{d_frames, d_crop_stream, d_boxes, box_stride, W, H, dims_};
         if (mode_ == 2) forward_hp(n_max, fuse_stem ? &fa : nullptr, d_out, d_out_rows, st);
         else forward_fused(n_max, fuse_stem ? &fa : nullptr, d_out, d_out_rows, st);
         BM_HIP(hipEventRecord(b, st));
@@ -424,6 +449,7 @@ private:
         x1s_ = dev_alloc<_Float16>(n * 2048 * 16, owned_);      // conv1 output of the second stage-0 block (k_osblock EMIT -> RECON)
         x2s_ = dev_alloc<_Float16>(n * 2048 * 16, owned_);      // branch sum of the first stage-0 block
         allow_lds(k_stem_resize_fused, STEM2_LDS);
+        allow_lds(k_stem_sized_fused, STEM2_LDS);
         allow_lds(k_osblock<0, 16, true, false, true, false>, Geo<0>::LDS_BYTES);
         allow_lds(k_osblock<0, 64, false, true, false, true>, Geo<0>::LDS_BYTES);
 #if BM_STAGE1_HANDOVER
@@ -437,9 +463,12 @@ private:
         allow_lds(k_head_batched<128, 512>, HeadGeo<128>::LDS_BYTES);
         fused_ready_ = true;
     }
-    struct FrameArgs { const uint8_t* const* frames; const int* crop_stream; const float* boxes; int box_stride, W, H; };
+    struct FrameArgs { const uint8_t* const* frames; const int* crop_stream; const float* boxes; int box_stride, W, H; const int* dims; };
     void forward_fused(int n, const FrameArgs* fa, float* d_out, const int* d_out_rows, hipStream_t st) {
-        if (fa)     // crop + resize + normalise fused into the stem (the resized crop never reaches HBM)
+        if (fa && fa->dims)     // the same with the frame size of each crop's own stream
+            hipLaunchKernelGGL(k_stem_sized_fused, dim3(n), dim3(512), STEM2_LDS, st, fa->frames, fa->crop_stream, fa->boxes,
+                               fa->box_stride, fa->dims, d_lut_, act_a_, w_stem_, d_count_);
+        else if (fa)     // crop + resize + normalise fused into the stem (the resized crop never reaches HBM)
             hipLaunchKernelGGL(k_stem_resize_fused, dim3(n), dim3(512), STEM2_LDS, st, fa->frames, fa->crop_stream, fa->boxes,
                                fa->box_stride, fa->W, fa->H, d_lut_, act_a_, w_stem_, d_count_);
         else
@@ -488,6 +517,7 @@ private:
             hw_stem_fused_ = upload(buf);
         }
         allow_lds(k_stem_resize_fused_hp, STEM2_LDS_HP);
+        allow_lds(k_stem_sized_fused_hp, STEM2_LDS_HP);
         static const int stage[6] = {0, 0, 1, 1, 2, 2}, cin[6] = {16, 64, 64, 96, 96, 128}, down[6] = {1, 0, 1, 0, 1, 0};
         for (int b = 0; b < 6; ++b) {
             hbp_[b] = make_blk_pack_hp(stage[b], cin[b], down[b]);
@@ -521,7 +551,10 @@ private:
         hp_ready_ = true;
     }
     void forward_hp(int n, const FrameArgs* fa, float* d_out, const int* d_out_rows, hipStream_t st) {
-        if (fa)     // crop + resize + normalise fused into the stem on raw pixel values (the resized crop never reaches HBM)
+        if (fa && fa->dims)     // the same with the frame size of each crop's own stream
+            hipLaunchKernelGGL(k_stem_sized_fused_hp, dim3(n), dim3(512), STEM2_LDS_HP, st, fa->frames, fa->crop_stream, fa->boxes,
+                               fa->box_stride, fa->dims, act_a_, hact_al_, hw_stem_fused_, d_count_);
+        else if (fa)     // crop + resize + normalise fused into the stem on raw pixel values (the resized crop never reaches HBM)
             hipLaunchKernelGGL(k_stem_resize_fused_hp, dim3(n), dim3(512), STEM2_LDS_HP, st, fa->frames, fa->crop_stream, fa->boxes,
                                fa->box_stride, fa->W, fa->H, act_a_, hact_al_, hw_stem_fused_, d_count_);
         else
@@ -591,6 +624,7 @@ private:
     std::unique_ptr<WideOsnetHP> wide_hp_;  // the fp32-grade family for the same widths (created when mode 2 is first selected)
     bool fused_ready_ = false, force_fp32_crops_ = false, fuse_stem_ = true;
     const double* obb_geo_ = nullptr;
+    const int* dims_ = nullptr;             // per-stream {W, H} table (set_frame_dims) or nullptr: one size, the scalar kernels
     int pad_ = 0;
     BlkPack bp_[6];
     unsigned char* w_stem_ = nullptr;

@@ -1453,13 +1453,28 @@ __global__ void __launch_bounds__(512, BM_HP_STEM_LDS_LO ? 4 : 2) k_stem_resize_
                                                               const int* __restrict__ count) {
     stem_resize_fused_body<true>(frames, crop_stream, boxes, box_stride, W, H, nullptr, out_hi, out_lo, wts, count);
 }
+// the table forms of the two stems (frame size of the crop's own stream, reid_kernels_v1.hpp: frame_dims_of): same body, same budget
+__global__ void __launch_bounds__(512, 4) k_stem_sized_fused(const uint8_t* const* frames, const int* crop_stream, const float* boxes,
+                                                          int box_stride, const int* dims, const float* lut, _Float16* __restrict__ out,
+                                                          const unsigned char* __restrict__ wts, const int* __restrict__ count) {
+    if (count && (int)blockIdx.x >= *count) return;
+    const FrameDims d = frame_dims_of(dims, crop_stream, blockIdx.x);
+    stem_resize_fused_body<false>(frames, crop_stream, boxes, box_stride, d.W, d.H, lut, out, nullptr, wts, count);
+}
+__global__ void __launch_bounds__(512, BM_HP_STEM_LDS_LO ? 4 : 2) k_stem_sized_fused_hp(const uint8_t* const* frames, const int* crop_stream, const float* boxes,
+                                                             int box_stride, const int* dims, _Float16* __restrict__ out_hi,
+                                                             _Float16* __restrict__ out_lo, const unsigned char* __restrict__ wts,
+                                                             const int* __restrict__ count) {
+    if (count && (int)blockIdx.x >= *count) return;
+    const FrameDims d = frame_dims_of(dims, crop_stream, blockIdx.x);
+    stem_resize_fused_body<true>(frames, crop_stream, boxes, box_stride, d.W, d.H, nullptr, out_hi, out_lo, wts, count);
+}
 
 // crop -> resize -> normalise into the stem's fp16 RGBX layout (interior only; the 3-pixel border and the
 // X channel of the buffer stay zero from allocation).  Same integer pipeline as k_crop_resize.
-__global__ void k_crop_resize_rgbx(const uint8_t* const* frames, const int* crop_stream, const float* boxes,
-                                   int box_stride, int W, int H, const float* lut, _Float16* out, int rows_per_block,
-                                   const int* count, int pad) {
-    if (count && (int)blockIdx.x >= *count) return;
+__device__ __forceinline__ void crop_resize_rgbx_body(const uint8_t* const* frames, const int* crop_stream, const float* boxes,
+                                                      int box_stride, int W, int H, const float* lut, _Float16* out, int rows_per_block,
+                                                      int pad) {
     const int i = blockIdx.x;
     const int dx = threadIdx.x;
     const uint8_t* frame = frames[crop_stream[i]];
@@ -1478,6 +1493,19 @@ __global__ void k_crop_resize_rgbx(const uint8_t* const* frames, const int* crop
         px[3] = (_Float16)0.f;
         *reinterpret_cast<h4*>(out + (((long)i * STEM_ROWS + dy + 3) * STEM_COLS + dx + 3) * 4) = px;
     }
+}
+__global__ void k_crop_resize_rgbx(const uint8_t* const* frames, const int* crop_stream, const float* boxes,
+                                   int box_stride, int W, int H, const float* lut, _Float16* out, int rows_per_block,
+                                   const int* count, int pad) {
+    if (count && (int)blockIdx.x >= *count) return;
+    crop_resize_rgbx_body(frames, crop_stream, boxes, box_stride, W, H, lut, out, rows_per_block, pad);
+}
+__global__ void k_crop_resize_rgbx_sized(const uint8_t* const* frames, const int* crop_stream, const float* boxes,
+                                         int box_stride, const int* dims, const float* lut, _Float16* out, int rows_per_block,
+                                         const int* count, int pad) {
+    if (count && (int)blockIdx.x >= *count) return;
+    const FrameDims d = frame_dims_of(dims, crop_stream, blockIdx.x);
+    crop_resize_rgbx_body(frames, crop_stream, boxes, box_stride, d.W, d.H, lut, out, rows_per_block, pad);
 }
 
 }  // namespace bm

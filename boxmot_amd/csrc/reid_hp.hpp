@@ -1496,10 +1496,9 @@ __global__ void __launch_bounds__(512) k_stem_hp(const _Float16* __restrict__ cr
 }
 
 // crop -> resize -> normalise into the stem's (hi, lo) fp16 RGBX planes (interior only; border and X channel stay zero)
-__global__ void k_crop_resize_rgbx_hl(const uint8_t* const* frames, const int* crop_stream, const float* boxes, int box_stride, int W,
-                                      int H, const float* lut, _Float16* out_hi, _Float16* out_lo, int rows_per_block, const int* count,
-                                      int pad) {
-    if (count && (int)blockIdx.x >= *count) return;
+__device__ __forceinline__ void crop_resize_rgbx_hl_body(const uint8_t* const* frames, const int* crop_stream, const float* boxes,
+                                                         int box_stride, int W, int H, const float* lut, _Float16* out_hi, _Float16* out_lo,
+                                                         int rows_per_block, int pad) {
     const int i = blockIdx.x;
     const int dx = threadIdx.x;
     const uint8_t* frame = frames[crop_stream[i]];
@@ -1522,6 +1521,20 @@ __global__ void k_crop_resize_rgbx_hl(const uint8_t* const* frames, const int* c
         *reinterpret_cast<h4*>(out_hi + o) = ph;
         *reinterpret_cast<h4*>(out_lo + o) = pl;
     }
+}
+__global__ void k_crop_resize_rgbx_hl(const uint8_t* const* frames, const int* crop_stream, const float* boxes, int box_stride, int W,
+                                      int H, const float* lut, _Float16* out_hi, _Float16* out_lo, int rows_per_block, const int* count,
+                                      int pad) {
+    if (count && (int)blockIdx.x >= *count) return;
+    crop_resize_rgbx_hl_body(frames, crop_stream, boxes, box_stride, W, H, lut, out_hi, out_lo, rows_per_block, pad);
+}
+// table form: the frame size of the crop's own stream (reid_kernels_v1.hpp: frame_dims_of)
+__global__ void k_crop_resize_rgbx_hl_sized(const uint8_t* const* frames, const int* crop_stream, const float* boxes, int box_stride,
+                                            const int* dims, const float* lut, _Float16* out_hi, _Float16* out_lo, int rows_per_block,
+                                            const int* count, int pad) {
+    if (count && (int)blockIdx.x >= *count) return;
+    const FrameDims d = frame_dims_of(dims, crop_stream, blockIdx.x);
+    crop_resize_rgbx_hl_body(frames, crop_stream, boxes, box_stride, d.W, d.H, lut, out_hi, out_lo, rows_per_block, pad);
 }
 
 }  // namespace bm

@@ -153,9 +153,19 @@ __device__ inline int obb_pixel(const uint8_t* frame, int W, int H, const double
 
 // RGBX = false: out T [n][256][128][3] normalised (k_crop_resize's layout); RGBX = true: fp16 RGBX with a 3-pixel zero border,
 // [n][262][136][4] (k_crop_resize_rgbx's layout: interior only, border and X channel stay zero from allocation)
+// Per-stream frame sizes: dims[stream] = {W, H} (two ints per stream, written by the host next to the crop -> stream table).  Every
+// thread of a workgroup works on one crop, so the lookup is one uniform load kept in scalar registers.  Each frame-addressing
+// kernel exists twice over one __device__ body: the scalar form (one W, H for the launch; all streams of the pass have one size)
+// and the `_sized` table form (the size of the crop's own frame).
+struct FrameDims { int W, H; };
+__device__ __forceinline__ FrameDims frame_dims_of(const int* dims, const int* crop_stream, long crop) {
+    const int s = crop_stream[crop];
+    return FrameDims{BM_UNIFORM_I32(dims[2 * s]), BM_UNIFORM_I32(dims[2 * s + 1])};
+}
+
 template <typename T, bool RGBX>
-__global__ void k_crop_resize_obb(const uint8_t* const* frames, const int* crop_stream, const double* geo, int W, int H, const float* lut,
-                                  T* out, int rows_per_block, int pad) {
+__device__ __forceinline__ void crop_resize_obb_body(const uint8_t* const* frames, const int* crop_stream, const double* geo, int W, int H,
+                                                     const float* lut, T* out, int rows_per_block, int pad) {
     const int i = blockIdx.x;
     const int dx = threadIdx.x;               // 0..127
     const uint8_t* frame = frames[crop_stream[i]];
@@ -183,9 +193,21 @@ __global__ void k_crop_resize_obb(const uint8_t* const* frames, const int* crop_
     }
 }
 
+template <typename T, bool RGBX>
+__global__ void k_crop_resize_obb(const uint8_t* const* frames, const int* crop_stream, const double* geo, int W, int H, const float* lut,
+                                  T* out, int rows_per_block, int pad) {
+    crop_resize_obb_body<T, RGBX>(frames, crop_stream, geo, W, H, lut, out, rows_per_block, pad);
+}
+template <typename T, bool RGBX>
+__global__ void k_crop_resize_obb_sized(const uint8_t* const* frames, const int* crop_stream, const double* geo, const int* dims,
+                                        const float* lut, T* out, int rows_per_block, int pad) {
+    const FrameDims d = frame_dims_of(dims, crop_stream, blockIdx.x);
+    crop_resize_obb_body<T, RGBX>(frames, crop_stream, geo, d.W, d.H, lut, out, rows_per_block, pad);
+}
+
 template <typename T>
-__global__ void k_crop_resize(const uint8_t* const* frames, const int* crop_stream, const float* boxes,
-                              int box_stride, int W, int H, const float* lut, T* out, int rows_per_block, int pad) {
+__device__ __forceinline__ void crop_resize_body(const uint8_t* const* frames, const int* crop_stream, const float* boxes,
+                                                 int box_stride, int W, int H, const float* lut, T* out, int rows_per_block, int pad) {
     const int i = blockIdx.x;
     const int dx = threadIdx.x;               // 0..127
     const uint8_t* frame = frames[crop_stream[i]];
@@ -202,6 +224,18 @@ __global__ void k_crop_resize(const uint8_t* const* frames, const int* crop_stre
             o[c] = (T)lut[c * 256 + v];
         }
     }
+}
+
+template <typename T>
+__global__ void k_crop_resize(const uint8_t* const* frames, const int* crop_stream, const float* boxes,
+                              int box_stride, int W, int H, const float* lut, T* out, int rows_per_block, int pad) {
+    crop_resize_body<T>(frames, crop_stream, boxes, box_stride, W, H, lut, out, rows_per_block, pad);
+}
+template <typename T>
+__global__ void k_crop_resize_sized(const uint8_t* const* frames, const int* crop_stream, const float* boxes,
+                                    int box_stride, const int* dims, const float* lut, T* out, int rows_per_block, int pad) {
+    const FrameDims d = frame_dims_of(dims, crop_stream, blockIdx.x);
+    crop_resize_body<T>(frames, crop_stream, boxes, box_stride, d.W, d.H, lut, out, rows_per_block, pad);
 }
 
 // ---------------------------------------------------------------------------

@@ -26,27 +26,63 @@ from boxmot_amd import _lib
 
 
 class FrameRing:
-    def __init__(self, n_slots: int, n_streams: int, rows: int, cols: int):
+    def __init__(self, n_slots: int, n_streams: int, rows: int | None = None, cols: int | None = None, sizes=None):
+        """``rows, cols``: one frame size for every stream; or ``sizes``: a ``(rows, cols)`` per stream (cameras of different
+        resolutions in one ring)."""
+        self.n_slots, self.n_streams = int(n_slots), int(n_streams)
+        if sizes is not None:
+            if rows is not None or cols is not None:
+                raise ValueError("FrameRing takes rows / cols or sizes, not both")
+            sizes = [tuple(int(v) for v in sz) for sz in sizes]
+            if len(sizes) != self.n_streams:
+                raise ValueError(f"FrameRing: sizes has {len(sizes)} entries for {self.n_streams} streams")
+            for s, sz in enumerate(sizes):
+                if len(sz) != 2 or sz[0] < 1 or sz[1] < 1:
+                    raise ValueError(f"stream {s}: size must be a positive (rows, cols), got {sz}")
+        else:
+            if rows is None or cols is None:
+                raise ValueError("FrameRing needs rows and cols, or sizes")
+            sizes = [(int(rows), int(cols))] * self.n_streams
+        self.sizes = sizes
+        self.mixed = len(set(sizes)) > 1
+        self.rows, self.cols = sizes[0]             # (of stream 0; the size of every stream on a uniform ring)
         self._lib = _lib.load()
-        self.n_slots, self.n_streams, self.rows, self.cols = int(n_slots), int(n_streams), int(rows), int(cols)
-        self._handle = self._lib.boxmot_hip_ingest_create(self.n_slots, self.n_streams, self.rows, self.cols)
+        if self.mixed:
+            r = np.array([sz[0] for sz in sizes], dtype=np.int32)
+            c = np.array([sz[1] for sz in sizes], dtype=np.int32)
+            self._handle = self._lib.boxmot_hip_ingest_create_sized(self.n_slots, self.n_streams, r.ctypes.data, c.ctypes.data)
+        else:
+            self._handle = self._lib.boxmot_hip_ingest_create(self.n_slots, self.n_streams, self.rows, self.cols)
         if not self._handle:
             raise RuntimeError(_lib.last_error())
         self._views = {}
         self._roots = {}
 
-    def host_view(self, slot: int) -> np.ndarray:
-        """(n_streams, rows, cols, 3) uint8 view of the slot's page-locked host memory."""
-        if slot not in self._views:
-            p = self._lib.boxmot_hip_ingest_host_ptr(self._handle, int(slot), 0)
+    def host_view(self, slot: int, stream: int | None = None) -> np.ndarray:
+        """``host_view(slot)``: (n_streams, rows, cols, 3) uint8 view of the slot's page-locked host memory (uniform rings);
+        ``host_view(slot, stream)``: that stream's (rows, cols, 3) frame (any ring)."""
+        if stream is not None:
+            stream = int(stream)
+            if not 0 <= stream < self.n_streams:
+                raise ValueError(f"stream {stream} out of range")
+            if not self.mixed:
+                return self.host_view(slot)[stream]
+            key = (slot, stream)
+        else:
+            if self.mixed:
+                raise ValueError("host_view(slot) needs one frame size; this ring's streams differ: use host_view(slot, stream)")
+            key = slot
+        if key not in self._views:
+            p = self._lib.boxmot_hip_ingest_host_ptr(self._handle, int(slot), stream or 0)
             if not p:
                 raise RuntimeError(_lib.last_error())
-            n = self.n_streams * self.rows * self.cols * 3
+            r, c = self.sizes[stream or 0]
+            n = (1 if self.mixed else self.n_streams) * r * c * 3
             buf = (ctypes.c_uint8 * n).from_address(p)
             root = np.frombuffer(buf, dtype=np.uint8)        # numpy collapses view chains onto this array: every slice a caller
-            self._roots[slot] = root                         # keeps holds a reference to IT (close() counts them)
-            self._views[slot] = root.reshape(self.n_streams, self.rows, self.cols, 3)
-        return self._views[slot]
+            self._roots[key] = root                          # keeps holds a reference to IT (close() counts them)
+            self._views[key] = root.reshape((r, c, 3) if self.mixed else (self.n_streams, r, c, 3))
+        return self._views[key]
 
     def submit(self, slot: int, n_streams: int | None = None) -> None:
         _lib.check(self._lib.boxmot_hip_ingest_submit(self._handle, int(slot), int(n_streams or self.n_streams)))

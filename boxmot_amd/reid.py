@@ -93,6 +93,67 @@ class HipReID:
                 self._handle, a.ctypes.data, a.shape[0], a.shape[1], 3, boxes.ctypes.data, n, boxes.shape[1], out.ctypes.data))
         return np.ascontiguousarray(np.transpose(out, (0, 3, 1, 2)))
 
+    def _batch(self, boxes_list, imgs):
+        """Validated inputs of a batch call, before anything reaches the library: (images, per-image box counts, the boxes of all
+        images stacked, image index of every box).  ``ValueError`` names the image at fault."""
+        boxes_list, imgs = list(boxes_list), list(imgs)
+        if len(boxes_list) != len(imgs):
+            raise ValueError(f"get_features_batch: {len(boxes_list)} box tables for {len(imgs)} images")
+        if not imgs:
+            raise ValueError("get_features_batch needs at least one image")
+        arrs, tables = [], []
+        for k, (b, im) in enumerate(zip(boxes_list, imgs)):
+            a = np.ascontiguousarray(im) if im is not None else None
+            if a is None or a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
+                raise ValueError(f"image {k}: ReID expects an (H, W, 3) uint8 BGR image")
+            arrs.append(a)
+            try:
+                tables.append(self._boxes(b if b is not None else ()))
+            except ValueError as e:
+                raise ValueError(f"image {k}: {e}") from None
+        counts = [len(t) for t in tables]
+        widths = {t.shape[1] for t in tables if len(t)}
+        if len(widths) > 1:
+            raise ValueError("get_features_batch: axis-aligned and oriented boxes cannot be mixed in one call")
+        w = widths.pop() if widths else 4
+        boxes = np.ascontiguousarray(np.concatenate([t for t in tables if len(t)], axis=0)) if sum(counts) else np.empty((0, w), np.float32)
+        box_image = np.repeat(np.arange(len(arrs), dtype=np.int32), counts).astype(np.int32)
+        return arrs, counts, boxes, box_image
+
+    def _image_tables(self, arrs):
+        ptrs = (ctypes.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+        rows = np.array([a.shape[0] for a in arrs], dtype=np.int32)
+        cols = np.array([a.shape[1] for a in arrs], dtype=np.int32)
+        return ptrs, rows, cols
+
+    def get_features_batch(self, boxes_list, imgs) -> list:
+        """``get_features`` for the boxes of many frames -- of any sizes -- in one device pass: ``boxes_list[k]`` are the boxes of
+        ``imgs[k]``.  Returns one ``(n_k, feature_dim)`` array per image (``(0, feature_dim)`` for an image without boxes), each equal to
+        ``get_features(boxes_list[k], imgs[k])``."""
+        arrs, counts, boxes, box_image = self._batch(boxes_list, imgs)
+        n = len(boxes)
+        out = np.empty((n, self.feature_dim), dtype=np.float32)
+        if n:
+            ptrs, rows, cols = self._image_tables(arrs)
+            _lib.check(self._lib.boxmot_hip_reid_compute_features_batch(
+                self._handle, ptrs, rows.ctypes.data, cols.ctypes.data, len(arrs), boxes.ctypes.data, box_image.ctypes.data, n,
+                boxes.shape[1], out.ctypes.data, n))
+        return [np.ascontiguousarray(p) for p in np.split(out, np.cumsum(counts)[:-1])]
+
+    def get_crops_batch(self, boxes_list, imgs) -> list:
+        """``get_crops`` for the boxes of many frames in one launch: one ``(n_k, 3, 256, 128)`` array per image."""
+        arrs, counts, boxes, box_image = self._batch(boxes_list, imgs)
+        n = len(boxes)
+        if n > self.max_crops:
+            raise ValueError("more boxes than max_crops")
+        out = np.empty((n, 256, 128, 3), dtype=np.float32)
+        if n:
+            ptrs, rows, cols = self._image_tables(arrs)
+            _lib.check(self._lib.boxmot_hip_reid_preprocess_batch(
+                self._handle, ptrs, rows.ctypes.data, cols.ctypes.data, len(arrs), boxes.ctypes.data, box_image.ctypes.data, n,
+                boxes.shape[1], out.ctypes.data))
+        return [np.ascontiguousarray(np.transpose(p, (0, 3, 1, 2))) for p in np.split(out, np.cumsum(counts)[:-1])]
+
     def last_time_ms(self):
         """(preprocess, backbone) device milliseconds of the last ``get_features`` chunk (HIP events)."""
         pre, proc = ctypes.c_double(0), ctypes.c_double(0)

@@ -33,7 +33,8 @@ def shard_streams(n_streams_total: int, rank: int, world: int) -> list[int]:
 
 class MultiStreamBotSort:
     def __init__(self, n_streams: int, max_tracks: int = 1024, max_dets: int = 256, emb_dim: int = 512,
-                 reid_weights=None, use_cmc: bool = False, cmc_method: str | None = None, is_obb: bool = False, **botsort_kwargs):
+                 reid_weights=None, use_cmc: bool = False, cmc_method: str | None = None, is_obb: bool = False, frame_sizes=None,
+                 **botsort_kwargs):
         # camera-motion compensation: the warp of a stream is supplied per frame with set_warp() (estimating it from the
         # images is the caller's, as for BotSort(cmc=...)); use_cmc only documents the intent.  cmc_method = "sof" / "ecc"
         # makes the handle estimate it itself from the frames it is given (host updates and device-resident steps alike)
@@ -41,6 +42,13 @@ class MultiStreamBotSort:
         unknown = set(botsort_kwargs) - set(BOTSORT_KEYS)
         if unknown:
             raise TypeError(f"unknown BoT-SORT options: {sorted(unknown)}")
+        # per-stream frame sizes: declared here (needed before step_device with frames) or taken from each stream's first frame
+        self._sizes = [None] * int(n_streams)
+        self._declared = False
+        self._own_cmc = cmc_method is not None          # the handle estimates camera motion itself: its estimators are made per size
+        self._had_frames = False                        # a call with frames has been accepted
+        if frame_sizes is not None:
+            self._sizes = self._check_sizes(frame_sizes, int(n_streams))
         self._lib = _lib.load()
         cfg = _lib.BotSortConfig()
         self._lib.boxmot_hip_botsort_default_config(ctypes.byref(cfg))
@@ -59,10 +67,49 @@ class MultiStreamBotSort:
         self._handle = self._lib.boxmot_hip_botsort_create(ctypes.byref(cfg))
         if not self._handle:
             raise RuntimeError(_lib.last_error())
+        if frame_sizes is not None:
+            self._declare_sizes()
         self._blob = None
         if reid_weights is not None:
             self._blob = load_weights(reid_weights)
             _lib.check(self._lib.boxmot_hip_botsort_set_reid_blob(self._handle, self._blob.ctypes.data, int(self._blob.size)))
+
+    @staticmethod
+    def _check_sizes(sizes, n_streams):
+        sizes = [tuple(int(v) for v in sz) for sz in sizes]
+        if len(sizes) != n_streams:
+            raise ValueError(f"frame_sizes has {len(sizes)} entries for {n_streams} streams")
+        for s, sz in enumerate(sizes):
+            if len(sz) != 2 or sz[0] < 1 or sz[1] < 1:
+                raise ValueError(f"stream {s}: frame size must be a positive (rows, cols), got {sz}")
+        return sizes
+
+    def _declare_sizes(self, sizes=None):
+        """hand the per-stream sizes to the handle (every stream's size is known); they are recorded once the handle has them"""
+        sizes = self._sizes if sizes is None else sizes
+        r = np.array([sz[0] for sz in sizes], dtype=np.int32)
+        c = np.array([sz[1] for sz in sizes], dtype=np.int32)
+        _lib.check(self._lib.boxmot_hip_botsort_set_frame_sizes(self._handle, r.ctypes.data, c.ctypes.data, len(sizes)))
+        self._sizes = list(sizes)
+        self._declared = True
+
+    def _check_frames(self, keep):
+        """Every image of a call, before any pointer goes down: uint8 (H, W, 3), and of the size its stream has had since its
+        first frame (or was declared with).  Returns the sizes as they stand after this call."""
+        sizes = list(self._sizes)
+        for s, im in enumerate(keep):
+            if im is None:
+                continue
+            if s >= len(sizes):
+                raise ValueError(f"stream {s}: the handle has {len(sizes)} streams")
+            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3 or im.shape[0] < 1 or im.shape[1] < 1:
+                raise ValueError(f"stream {s}: expected an (H, W, 3) uint8 BGR frame, got {im.dtype} {im.shape}")
+            if sizes[s] is None:
+                sizes[s] = (int(im.shape[0]), int(im.shape[1]))
+            elif tuple(im.shape[:2]) != sizes[s]:
+                raise ValueError(f"stream {s}: frame is {im.shape[0]} x {im.shape[1]}, this stream's frames are "
+                                 f"{sizes[s][0]} x {sizes[s][1]} (a stream keeps the size of its first frame)")
+        return sizes
 
     # ---- host buffers: list of (n_s, 6) dets, optional list of embs / frames ----
     def update_batch(self, dets_list, imgs=None, embs_list=None, ring=None, slot: int = 0):
@@ -80,10 +127,27 @@ class MultiStreamBotSort:
             emb_ptrs = (ctypes.c_void_p * S)(*[e.ctypes.data if len(e) else None for e in embs])
         img_ptrs, ir, ic = None, 1, 1
         keep = []
+        pending_sizes = None        # first-frame sizes of this call: recorded once the library has accepted the frames
         if imgs is not None:
             keep = [None if im is None else np.ascontiguousarray(im) for im in imgs]
             first = next((im for im in keep if im is not None), None)
             if first is not None:       # every entry None: all streams keep their previously uploaded frame
+                sizes = self._check_frames(keep)
+                known = [sz for sz in sizes if sz is not None]
+                if not self._declared and len(set(known)) > 1:
+                    # frames of different sizes: the handle needs every stream's size; a stream that has not sent a frame yet
+                    # cannot be declared
+                    missing = [k for k, sz in enumerate(sizes) if sz is None]
+                    if missing:
+                        raise ValueError(f"stream {missing[0]}: no frame yet, and the streams' frames differ in size: pass frame_sizes= "
+                                         "to the constructor or give every stream its first frame in one call")
+                    if self._own_cmc and self._had_frames:
+                        # the handle made its camera-motion estimator for the one size it had seen: sizes cannot be added later
+                        k = next(k for k, sz in enumerate(sizes) if self._sizes[k] is None and sz != known[0])
+                        raise ValueError(f"stream {k}: frame is {sizes[k][0]} x {sizes[k][1]}, the frames so far were {known[0][0]} x {known[0][1]}: "
+                                         "with cmc_method the sizes are declared up front (frame_sizes=) or all arrive in the first call")
+                    self._declare_sizes(sizes)
+                pending_sizes = sizes
                 ir, ic = first.shape[0], first.shape[1]
                 img_ptrs = (ctypes.c_void_p * S)(*[None if im is None else im.ctypes.data for im in keep])
         cap = max(int(rows.max()) if S else 0, 1)
@@ -92,21 +156,34 @@ class MultiStreamBotSort:
         out_rows = np.zeros(S, dtype=np.int32)
         if ring is not None:
             stream = self._lib.boxmot_hip_botsort_stream(self._handle)
+            if getattr(ring, "mixed", False) and not self._declared:
+                if len(ring.sizes) != self.n_streams:
+                    raise ValueError(f"the ring has {len(ring.sizes)} streams, the handle {self.n_streams}")
+                for k, (have, want) in enumerate(zip(self._sizes, ring.sizes)):
+                    if have is not None and have != tuple(want):
+                        raise ValueError(f"stream {k}: the ring's frames are {want[0]} x {want[1]}, this stream's frames are {have[0]} x {have[1]}")
+                self._declare_sizes([tuple(sz) for sz in ring.sizes])
             ring.wait(slot, stream)
             ok = self._lib.boxmot_hip_botsort_update_batch_frames(
                 self._handle, S, det_ptrs, rows.ctypes.data, emb_ptrs, self.emb_dim if embs is not None else 0,
                 ctypes.c_void_p(ring.device_frames(slot)), ring.rows, ring.cols, out_ptrs, cap, out_rows.ctypes.data)
             ring.release(slot, stream)
             _lib.check(ok)
+            self._had_frames = True
             return [TrackResults(o[:n, :self._out_cols].copy()) for o, n in zip(outs, out_rows)]
         _lib.check(self._lib.boxmot_hip_botsort_update_batch(
             self._handle, S, det_ptrs, rows.ctypes.data, emb_ptrs, self.emb_dim if embs is not None else 0,
             img_ptrs, ir, ic, 3, out_ptrs, cap, out_rows.ctypes.data))
+        if pending_sizes is not None:
+            self._sizes, self._had_frames = pending_sizes, True
         return [TrackResults(o[:n, :self._out_cols].copy()) for o, n in zip(outs, out_rows)]
 
     # ---- device-resident step: arguments are raw device addresses (ints) ----
     def step_device(self, d_dets: int, d_det_rows: int, d_embs: int | None, d_frames: int | None, rows: int, cols: int,
                     d_out: int, d_out_rows: int) -> None:
+        """Device-resident step; all arguments are device addresses except ``rows, cols``, the one size of the frames behind
+        ``d_frames``.  On a handle made with ``frame_sizes=`` (the way to give streams of different sizes to this call, which sees
+        no host image) ``rows, cols`` are not used: pass 0, 0."""
         _lib.check(self._lib.boxmot_hip_botsort_step_device(
             self._handle, d_dets, d_det_rows, d_embs, d_frames, rows, cols, d_out, d_out_rows))
 

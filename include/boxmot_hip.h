@@ -216,6 +216,13 @@ int boxmot_hip_botsort_state_dump(
  *            (matching.py:85-107) where the step evaluated it -- NaN elsewhere: the pairs behind the IoU gate are never evaluated on
  *            the sparse path, every pair is on the dense fallback (more than 4096 ungated pairs).
  * Row r is the r-th track of the stage's track list, column c the c-th detection of its detection list, in the reference's order. */
+/* Per-stream frame sizes of a multi-stream handle (BoT-SORT and ByteTrack): stream s sends (image_rows[s], image_cols[s], 3) frames.
+   A camera's size is a property of the stream, so it is declared once; afterwards the scalar image_rows / image_cols arguments of
+   update_batch, update_batch_frames and step_device are not used for this handle.  n_streams must be the handle's; a stream that
+   already has frames of another size is an error naming the stream.  Streams of one size are launched exactly as without the call;
+   sizes that differ make the ReID crop kernels read each stream's size from a device table, and cmc_method "sof" / "ecc" keeps one
+   estimator per distinct size.  A handle that never calls this is untouched. */
+int boxmot_hip_botsort_set_frame_sizes(BoxMOTHipBotSort* handle, const int* image_rows, const int* image_cols, int n_streams);
 int boxmot_hip_botsort_debug_costs_enable(BoxMOTHipBotSort* handle, int on);
 int boxmot_hip_botsort_debug_costs(
     BoxMOTHipBotSort* handle, int stream, int stage, int plane,
@@ -238,6 +245,18 @@ int boxmot_hip_reid_compute_features(
 int boxmot_hip_reid_preprocess(
     BoxMOTHipReID* handle, const uint8_t* image, int image_rows, int image_cols, int image_channels,
     const float* boxes, int n_boxes, int box_cols, float* out_crops);
+/* Boxes of many images in one device pass: images[k] is (image_rows[k], image_cols[k], 3) uint8 BGR -- the sizes may differ --,
+   box_image[i] is the image that box i lies in, boxes as for compute_features (all rows of one call have box_cols columns).
+   out (n_boxes, feature_dim) in the order of the boxes; more than max_crops boxes run in passes of max_crops.  Every crop is what
+   compute_features returns for that box on its own image: when the sizes differ the kernels take each frame's size from a
+   per-image table on the device, when they are equal the launches are those of compute_features. */
+int boxmot_hip_reid_compute_features_batch(
+    BoxMOTHipReID* handle, const uint8_t* const* images, const int* image_rows, const int* image_cols, int n_images,
+    const float* boxes, const int* box_image, int n_boxes, int box_cols, float* out_features, int out_capacity_rows);
+/* the same for the intermediate crops (n_boxes <= max_crops) */
+int boxmot_hip_reid_preprocess_batch(
+    BoxMOTHipReID* handle, const uint8_t* const* images, const int* image_rows, const int* image_cols, int n_images,
+    const float* boxes, const int* box_image, int n_boxes, int box_cols, float* out_crops);
 
 /* device milliseconds (HIP events on the handle's stream) of the last compute_features: crop / resize / normalise, and the
  * backbone forward (cf. boxmot_botsort_last_reid_{preprocess,process}_time_ms, c_api.hpp:58-59) */
@@ -307,6 +326,9 @@ int boxmot_hip_sof_debug_map(BoxMOTHipSof* handle, int stream, int which, void* 
  * ------------------------------------------------------------------------------------------------ */
 typedef struct BoxMOTHipIngest BoxMOTHipIngest;
 BoxMOTHipIngest* boxmot_hip_ingest_create(int n_slots, int n_streams, int image_rows, int image_cols);
+/* the same for streams whose frames differ in size: stream s is (image_rows[s], image_cols[s], 3); host_ptr(slot, stream) gives
+   that stream's frame; one pinned allocation and one DMA per slot (frames at 256-byte aligned offsets) */
+BoxMOTHipIngest* boxmot_hip_ingest_create_sized(int n_slots, int n_streams, const int* image_rows, const int* image_cols);
 void boxmot_hip_ingest_destroy(BoxMOTHipIngest* handle);
 uint8_t* boxmot_hip_ingest_host_ptr(BoxMOTHipIngest* handle, int slot, int stream);
 const uint8_t* const* boxmot_hip_ingest_device_frames(BoxMOTHipIngest* handle, int slot);
@@ -500,6 +522,10 @@ int boxmot_hip_strongsort_step_device_frames(BoxMOTHipStrongSort* handle, const 
                                               int* d_out_rows);
 int boxmot_hip_strongsort_reid_kernel_ms(BoxMOTHipStrongSort* handle, double* out_ms, int* out_launches);
 int boxmot_hip_strongsort_set_reid_mode(BoxMOTHipStrongSort* handle, int mode);
+/* per-stream frame sizes (boxmot_hip_botsort_set_frame_sizes) for the DeepOCSORT / OC-SORT and StrongSORT handles (update_batch, step_device_frames).  asso_func centroid normalises by
+   one frame diagonal per handle: sizes that differ are refused on such a handle, with a message that says so. */
+int boxmot_hip_deepocsort_set_frame_sizes(BoxMOTHipDeepOcSort* handle, const int* image_rows, const int* image_cols, int n_streams);
+int boxmot_hip_strongsort_set_frame_sizes(BoxMOTHipStrongSort* handle, const int* image_rows, const int* image_cols, int n_streams);
 void* boxmot_hip_strongsort_stream(BoxMOTHipStrongSort* handle);
 int boxmot_hip_strongsort_synchronize(BoxMOTHipStrongSort* handle);
 /* as boxmot_hip_deepocsort_set_crop_bound */
