@@ -8,81 +8,11 @@
 //
 // Built two ways: by hipcc for gfx950 (tests/test_gpu_gemm_kat.py), and with -DKAT_EMU by a host clang against tests/host_emu/hip_shim.hpp,
 // where the same kernels run on CPU threads (tests/test_gemm_kat_emu.py).  Nothing in boxmot_amd/ includes this file.
-#ifdef KAT_EMU
-#include "../host_emu/hip_shim.hpp"
-#else
-#include <hip/hip_runtime.h>
-#endif
-
-#include <cstdint>
-#include <cstdlib>
-#include <cstring>
-#include <functional>
-#include <vector>
+#include "kat_harness.hpp"
 
 #include "../../boxmot_amd/csrc/gemm_f16.hpp"
 
 using namespace bm;
-
-#ifdef KAT_EMU
-thread_local EmuDim3 threadIdx;
-thread_local EmuDim3 blockIdx;
-EmuDim3 blockDim;
-EmuDim3 gridDim;
-EmuBlock* g_emu_block = nullptr;
-unsigned char* g_emu_dynamic_lds = nullptr;
-EmuMfmaBuf* g_emu_mfma = nullptr;
-
-namespace {
-struct TA { const std::function<void()>* fn; int tid, bx; };
-void* tmain(void* p) {
-    TA* a = static_cast<TA*>(p);
-    threadIdx.x = a->tid; blockIdx.x = a->bx; blockIdx.y = 0;
-    (*a->fn)();
-    return nullptr;
-}
-// one workgroup after the other; LDS poisoned (0xFF: fp16 NaN) before each
-void emu_launch(unsigned grid, int nthr, size_t lds_bytes, const std::function<void()>& fn) {
-    static EmuBlock block;
-    static EmuMfmaBuf mf;
-    static std::vector<unsigned char> lds;
-    if (lds.size() < lds_bytes + 64) lds.resize(lds_bytes + 64);
-    g_emu_block = &block; g_emu_mfma = &mf;
-    g_emu_dynamic_lds = reinterpret_cast<unsigned char*>((reinterpret_cast<uintptr_t>(lds.data()) + 15) & ~uintptr_t(15));
-    blockDim.x = nthr; gridDim.x = grid; gridDim.y = 1;
-    block.block_barrier.init(nthr);
-    for (int w = 0; w < EMU_MAX_WAVES; ++w) block.wave_barrier[w].init(EMU_WAVE);
-    for (unsigned bx = 0; bx < grid; ++bx) {
-        std::memset(lds.data(), 0xFF, lds.size());
-        std::vector<TA> ta(nthr);
-        for (int t = 0; t < nthr; ++t) ta[t] = TA{&fn, t, (int)bx};
-        emu_run_threads(nthr, tmain, ta.data(), sizeof(ta[0]), 1 << 18);
-    }
-}
-}  // namespace
-
-#define KAT_LAUNCH(kern, grid, block, lds, ...) emu_launch((unsigned)(grid), (block), (lds), [&]() { kern(__VA_ARGS__); })
-#define KAT_SET_LDS(kern, bytes) 0
-static int dev_alloc(void** p, size_t n) { *p = std::malloc(n ? n : 1); return *p ? 0 : -2; }
-static void dev_free(void* p) { std::free(p); }
-static int h2d(void* d, const void* h, size_t n) { if (n) std::memcpy(d, h, n); return 0; }
-static int d2h(void* h, const void* d, size_t n) { if (n) std::memcpy(h, d, n); return 0; }
-static int dev_finish() { return 0; }
-#else
-#define KAT_LAUNCH(kern, grid, block, lds, ...) hipLaunchKernelGGL(kern, dim3((unsigned)(grid)), dim3(block), (lds), 0, __VA_ARGS__)
-// hipFuncSetAttribute once per instantiation, as the engines' constructors do
-#define KAT_SET_LDS(kern, bytes)                                                                                                           \
-    ([]() {                                                                                                                                \
-        static const int rc = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (bytes)) \
-                                      == hipSuccess ? 0 : -2;                                                                              \
-        return rc;                                                                                                                         \
-    }())
-static int dev_alloc(void** p, size_t n) { return hipMalloc(p, n ? n : 1) == hipSuccess ? 0 : -2; }
-static void dev_free(void* p) { if (p) (void)hipFree(p); }
-static int h2d(void* d, const void* h, size_t n) { return !n || hipMemcpy(d, h, n, hipMemcpyHostToDevice) == hipSuccess ? 0 : -2; }
-static int d2h(void* h, const void* d, size_t n) { return !n || hipMemcpy(h, d, n, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -2; }
-static int dev_finish() { return hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess ? 0 : -2; }
-#endif
 
 namespace {
 
