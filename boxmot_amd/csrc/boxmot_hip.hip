@@ -332,142 +332,42 @@ struct BoxMOTHipIngest : DeviceBound {
     }
 };
 
-struct BoxMOTHipBotSort : DeviceBound {
-    BoxMOTHipBotSortConfig cfg{};
+// What the three tracker handles share on the host: the weight blob and ReID engine, the staging tables of the per-stream inputs and
+// results, the frames a host update uploads, the crop list, pending camera-motion warps, the record of the tracker's tables
+// (growth), the two-stage ReID pipeline and the per-stream frame sizes.
+namespace {
+struct HandleCore : DeviceBound {
     std::string reid_path;
     std::vector<float> reid_blob;            // host copy of the weight blob the engine was built from (path or set_reid_blob): growth rebuilds from it
-    bm::BotSortStepArgs args{};
     std::vector<void*> owned;
     hipStream_t stream = nullptr;
-    hipEvent_t ev[2]{};
-    hipEvent_t timer_ev[2]{};
-    int S = 1, cap = 0, nd = 0, dim = 0, n_lists = 1;
+    int S = 1, cap = 0, nd = 0, dim = 0;
+    int det_cols = bm::DET_COLS, out_cols = bm::OUT_COLS;      // 7 / 9 on an oriented handle; set at build
     // io staging
-    float* d_dets = nullptr;
-    int* d_ndets = nullptr;
-    float* d_embs = nullptr;
-    float* d_out = nullptr;
-    int* d_out_n = nullptr;
-    int* d_list_sel = nullptr;
-    int* d_fc_set = nullptr;
+    float* d_dets = nullptr; int* d_ndets = nullptr; float* d_embs = nullptr; float* d_out = nullptr; int* d_out_n = nullptr;
     double* d_warp = nullptr;      // [S][6] camera-motion warps for the next update of each stream
     int* d_warp_flag = nullptr;
     std::vector<float> h_dets, h_out;
-    std::vector<int> h_ndets, h_out_n, h_list_sel, h_fc_set, h_warp_flag;
+    std::vector<int> h_ndets, h_out_n, h_warp_flag;
     std::vector<double> h_warp;
     // frames owned by the handle (host API)
     std::vector<uint8_t*> frame_bufs;
     size_t frame_bytes = 0;
     int frame_rows = 0, frame_cols = 0;
     const uint8_t** d_frames = nullptr;
-    // reid
     std::unique_ptr<bm::ReidEngine> reid;
-    int reid_mode = 0, reid_pad = 0;
-    bool is_obb = false;                         // oriented detections (7 columns in, 9 out, 10-state filter): config.is_obb
-    float* d_cmc_boxes = nullptr;                // [S][nd][4] enclosing boxes of the oriented detections: the SOF estimator's mask boxes
-    int det_cols() const { return is_obb ? bm::obb::DET_COLS : bm::DET_COLS; }
-    int out_cols() const { return is_obb ? bm::obb::OUT_COLS : bm::OUT_COLS; }
-    int kf_stride() const { return is_obb ? bm::obb::KF_STRIDE : bm::KF_STRIDE; }
-    bool use_ecc = false;                        // cmc_method = "ecc": the estimator runs inside update on the uploaded frame
-    std::unique_ptr<BoxMOTHipEcc> ecc;
-    bool use_sof = false;                        // cmc_method = "sof" (configs/trackers/botsort.yaml): likewise, masked by the frame's detections
-    bool cmc_with_fc_set = false;                // one update with a frame-counter preset that is NOT a per-class fan-out call (compat adapter's first
-                                                 // real frame after empty ones): the estimator sees the frame as it does in the reference
-    std::unique_ptr<BoxMOTHipSof> sof;
-    // per-stream frame sizes (boxmot_hip_botsort_set_frame_sizes): empty = one size per handle, taken from the calls' scalar
-    // arguments.  d_fs_dims is the {W, H} table the `_sized` crop kernels read (beside d_crop_stream; written when the sizes are
-    // set, not per frame); it is handed to the engine only when the sizes differ.  Handle-owned camera-motion estimation keeps one
-    // estimator per DISTINCT size; each is made for all S streams and serves the streams of its size under their own indices.
-    std::vector<int> fs_rows, fs_cols;
-    int* d_fs_dims = nullptr;
-    bool fs_mixed = false;
-    std::map<std::pair<int, int>, std::unique_ptr<BoxMOTHipSof>> sof_by_size;
-    std::map<std::pair<int, int>, std::unique_ptr<BoxMOTHipEcc>> ecc_by_size;
-    int* d_crop_count = nullptr;
-    int* d_crop_stream = nullptr;
-    float* d_crop_boxes = nullptr;
-    int* d_crop_row = nullptr;
-    long long* d_phase_clock = nullptr;
-    // parity debugging (boxmot_hip_botsort_debug_costs_enable): copies of the association cost matrices of the last step
-    bool dbg_costs = false;
-    double* d_dbg_cost = nullptr;
-    int* d_dbg_shape = nullptr;
-    int dbg_cap = 0, dbg_nd = 0;
-    double last_track_ms = 0, last_reid_pre_ms = 0, last_reid_proc_ms = 0;
-    // growth of the tables (grow_tables): what botsort_allocate handed out, in order; slots in use per stream after the last
-    // host update (-1 = unknown: a device-resident step ran since)
-    std::vector<std::pair<void*, size_t>> table_rec;
-    std::vector<int> h_used, h_count_buf;
-    int n_grows = 0;
-    // step_device as a two-stage pipeline over consecutive asynchronous calls (see StreamIo below: the same scheme): the ReID pass of
-    // frame t + 1 on `reid_stream` while the frame step of frame t runs on `stream`, alternating embedding tables.
-    hipStream_t reid_stream = nullptr;
-    float* d_embs_alt = nullptr;
-    hipEvent_t ev_reid_done[2] = {}, ev_embs_free[2] = {}, ev_main = nullptr;
-    int pipe_slot = 0;
-    bool pipe = true;
-    bool engine_on_main = false;
-    bool stream_exposed = false;        // boxmot_hip_botsort_stream() was handed out (see StreamIo)
-
-    ~BoxMOTHipBotSort() {
-        if (reid_stream) (void)hipStreamSynchronize(reid_stream);
-        if (stream) (void)hipStreamSynchronize(stream);
-        for (hipEvent_t e : ev_reid_done) if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : ev_embs_free) if (e) (void)hipEventDestroy(e);
-        if (ev_main) (void)hipEventDestroy(ev_main);
-        if (reid_stream) (void)hipStreamDestroy(reid_stream);
-        reid.reset();
-        for (void* p : owned) (void)hipFree(p);
-        for (auto* p : frame_bufs) if (p) (void)hipFree(p);
-        for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-        for (auto& e : timer_ev) if (e) (void)hipEventDestroy(e);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-};
-
-// Host-side plumbing shared by the DeepOCSORT and StrongSORT handles: pinned-down staging of the per-stream inputs,
-// the frames and ReID engine for "embeddings not supplied", pending camera-motion warps, result read-back.
-struct StreamIo : DeviceBound {
-    std::string reid_path;
-    std::vector<float> reid_blob;            // host copy of the weight blob (see BoxMOTHipBotSort::reid_blob)
-    std::vector<void*> owned;
-    hipStream_t stream = nullptr;
-    int S = 1, cap = 0, nd = 0, dim = 0;
-    int det_cols = bm::DET_COLS, out_cols = bm::OUT_COLS;      // 7 / 9 on an oriented handle (OC-SORT with is_obb)
-    float* d_dets = nullptr; int* d_ndets = nullptr; float* d_embs = nullptr; float* d_out = nullptr; int* d_out_n = nullptr;
-    double* d_warp = nullptr; int* d_warp_flag = nullptr;
-    std::vector<float> h_dets, h_out;
-    std::vector<int> h_ndets, h_out_n, h_warp_flag;
-    std::vector<double> h_warp;
-    std::vector<uint8_t*> frame_bufs;
-    size_t frame_bytes = 0;
-    int frame_rows = 0, frame_cols = 0;
-    const uint8_t** d_frames = nullptr;
-    std::unique_ptr<bm::ReidEngine> reid;
-    int reid_mode = -1;             // set_reid_mode's last value (-1: the engine's default), re-applied when the engine is re-made
     int* d_crop_count = nullptr; int* d_crop_stream = nullptr; float* d_crop_boxes = nullptr; int* d_crop_row = nullptr;
-    // set_crop_bound: host-declared upper bound on the ReID crops of a device-resident step (-1: none, the count is read back);
-    // d_crop_count[1] = "the count exceeded the bound"
-    int crop_bound = -1;
-    bool bounded_step_pending = false;      // a step sized by crop_bound was queued since the overflow flag was last read (io_check_crop_bound)
-    // growth of the tables: what the tracker's allocate function handed out, in order; tracks per stream after the last host
-    // update (-1 = unknown: a device-resident step ran since)
+    // growth of the tables: what the tracker's allocate function handed out, in order; slots in use per stream after the last
+    // host update (-1 = unknown: a device-resident step ran since)
     std::vector<std::pair<void*, size_t>> table_rec;
     std::vector<int> h_used;
     int n_grows = 0;
-    // device-resident steps upload pending warps from a small ring of staging slots (an event per slot): the host does not wait for
-    // the stream -- i.e. for the previous step's ReID pass -- every time a warp is set
-    static constexpr int WARP_SLOTS = 8;
-    std::vector<double> warp_stage[WARP_SLOTS];
-    std::vector<int> warp_flag_stage[WARP_SLOTS];
-    hipEvent_t warp_ev[WARP_SLOTS] = {};
-    unsigned warp_slot = 0;
-    // step_device_frames as a two-stage pipeline over consecutive (asynchronous) calls: the ReID pass of frame t + 1 is enqueued on
-    // `reid_stream` and runs while the frame step of frame t -- a handful of workgroups, one per stream, for milliseconds -- is
-    // still on `stream`.  A frame's embeddings do not depend on the previous frame's step (the crops come from the detections), so
-    // only the embedding table is double-buffered: ReID(t) writes table t & 1 after step(t - 2) has read it (ev_embs_free), step(t)
-    // starts after ReID(t) (ev_reid_done).  Every ReID pass is followed by its step on `stream`, so waiting for `stream` waits for
-    // both.  BOXMOT_HIP_PIPELINE=0 keeps everything on `stream` (A/B switch, profiles/r5_pipeline_ab.txt).
+    // The device-resident step with in-handle ReID as a two-stage pipeline over consecutive (asynchronous) calls: the ReID pass of
+    // frame t + 1 is enqueued on `reid_stream` and runs while the frame step of frame t -- a handful of workgroups, one per stream,
+    // for milliseconds -- is still on `stream`.  A frame's embeddings do not depend on the previous frame's step (the crops come from
+    // the detections), so only the embedding table is double-buffered: ReID(t) writes table t & 1 after step(t - 2) has read it
+    // (ev_embs_free), step(t) starts after ReID(t) (ev_reid_done).  Every ReID pass is followed by its step on `stream`, so waiting
+    // for `stream` waits for both.  BOXMOT_HIP_PIPELINE=0 keeps everything on `stream` (A/B switch, profiles/r5_pipeline_ab.txt).
     hipStream_t reid_stream = nullptr;
     float* d_embs_alt = nullptr;
     hipEvent_t ev_reid_done[2] = {}, ev_embs_free[2] = {}, ev_main = nullptr;
@@ -475,16 +375,19 @@ struct StreamIo : DeviceBound {
     bool pipe = true;
     bool engine_on_main = false;        // the engine / crop list were last used on `stream` (host-update paths)
     bool stream_exposed = false;        // *_stream() was handed out: the caller may order its inputs on `stream` -- every ReID pass waits for it
-    int* d_ndets_step[2] = {};          // [S] each: the detection counts a bounded step reads (-1 everywhere after a bound overflow)
-    const int* step_ndets = nullptr;    // what the frame step of the current step_device_frames call takes as n_dets
-    // per-stream frame sizes (boxmot_hip_{deepocsort,strongsort}_set_frame_sizes; as BoxMOTHipBotSort::fs_rows): empty = one size per handle
+    // per-stream frame sizes (*_set_frame_sizes): empty = one size per handle, taken from the calls' scalar arguments.  d_fs_dims is
+    // the [S][2] {W, H} table the `_sized` crop kernels read (written when the sizes are set, not per frame); it is handed to the
+    // engine only when the sizes differ.
     std::vector<int> fs_rows, fs_cols;
-    int* d_fs_dims = nullptr;           // [S][2] {W, H}: handed to the engine only when the sizes differ
+    int* d_fs_dims = nullptr;
     bool fs_mixed = false;
-    ~StreamIo() {
+
+    void sync_streams() {
         if (reid_stream) (void)hipStreamSynchronize(reid_stream);
         if (stream) (void)hipStreamSynchronize(stream);
-        for (hipEvent_t e : warp_ev) if (e) (void)hipEventDestroy(e);
+    }
+    ~HandleCore() {
+        sync_streams();
         for (hipEvent_t e : ev_reid_done) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : ev_embs_free) if (e) (void)hipEventDestroy(e);
         if (ev_main) (void)hipEventDestroy(ev_main);
@@ -493,6 +396,68 @@ struct StreamIo : DeviceBound {
         for (void* p : owned) (void)hipFree(p);
         for (auto* p : frame_bufs) if (p) (void)hipFree(p);
         if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+}  // namespace
+
+struct BoxMOTHipBotSort : HandleCore {
+    BoxMOTHipBotSortConfig cfg{};
+    bm::BotSortStepArgs args{};
+    hipEvent_t ev[2]{};
+    hipEvent_t timer_ev[2]{};
+    int n_lists = 1;
+    int* d_list_sel = nullptr;
+    int* d_fc_set = nullptr;
+    std::vector<int> h_list_sel, h_fc_set;
+    int reid_mode = 0, reid_pad = 0;
+    bool is_obb = false;                         // oriented detections (7 columns in, 9 out, 10-state filter): config.is_obb
+    float* d_cmc_boxes = nullptr;                // [S][nd][4] enclosing boxes of the oriented detections: the SOF estimator's mask boxes
+    bool use_ecc = false;                        // cmc_method = "ecc": the estimator runs inside update on the uploaded frame
+    std::unique_ptr<BoxMOTHipEcc> ecc;
+    bool use_sof = false;                        // cmc_method = "sof" (configs/trackers/botsort.yaml): likewise, masked by the frame's detections
+    bool cmc_with_fc_set = false;                // one update with a frame-counter preset that is NOT a per-class fan-out call (compat adapter's first
+                                                 // real frame after empty ones): the estimator sees the frame as it does in the reference
+    std::unique_ptr<BoxMOTHipSof> sof;
+    // with per-stream frame sizes, handle-owned camera-motion estimation keeps one estimator per DISTINCT size; each is made for all
+    // S streams and serves the streams of its size under their own indices
+    std::map<std::pair<int, int>, std::unique_ptr<BoxMOTHipSof>> sof_by_size;
+    std::map<std::pair<int, int>, std::unique_ptr<BoxMOTHipEcc>> ecc_by_size;
+    long long* d_phase_clock = nullptr;
+    // parity debugging (boxmot_hip_botsort_debug_costs_enable): copies of the association cost matrices of the last step
+    bool dbg_costs = false;
+    double* d_dbg_cost = nullptr;
+    int* d_dbg_shape = nullptr;
+    int dbg_cap = 0, dbg_nd = 0;
+    double last_track_ms = 0, last_reid_pre_ms = 0, last_reid_proc_ms = 0;
+    std::vector<int> h_count_buf;
+
+    ~BoxMOTHipBotSort() {
+        sync_streams();
+        for (auto& e : ev) if (e) (void)hipEventDestroy(e);
+        for (auto& e : timer_ev) if (e) (void)hipEventDestroy(e);
+    }
+};
+
+// The DeepOCSORT and StrongSORT handles: host updates stage through io_stage / io_read_back, device-resident steps upload pending
+// warps from a ring and may size their ReID launches by a declared crop bound.
+struct StreamIo : HandleCore {
+    int reid_mode = -1;             // set_reid_mode's last value (-1: the engine's default), re-applied when the engine is re-made
+    // set_crop_bound: host-declared upper bound on the ReID crops of a device-resident step (-1: none, the count is read back);
+    // d_crop_count[1] = "the count exceeded the bound"
+    int crop_bound = -1;
+    bool bounded_step_pending = false;      // a step sized by crop_bound was queued since the overflow flag was last read (io_check_crop_bound)
+    // device-resident steps upload pending warps from a small ring of staging slots (an event per slot): the host does not wait for
+    // the stream -- i.e. for the previous step's ReID pass -- every time a warp is set
+    static constexpr int WARP_SLOTS = 8;
+    std::vector<double> warp_stage[WARP_SLOTS];
+    std::vector<int> warp_flag_stage[WARP_SLOTS];
+    hipEvent_t warp_ev[WARP_SLOTS] = {};
+    unsigned warp_slot = 0;
+    int* d_ndets_step[2] = {};          // [S] each: the detection counts a bounded step reads (-1 everywhere after a bound overflow)
+    const int* step_ndets = nullptr;    // what the frame step of the current step_device_frames call takes as n_dets
+    ~StreamIo() {
+        sync_streams();
+        for (hipEvent_t e : warp_ev) if (e) (void)hipEventDestroy(e);
     }
 };
 
@@ -544,38 +509,267 @@ void release(std::vector<void*>& owned, void* p) {
         if (owned[i] == p) { owned.erase(owned.begin() + (long)i); (void)hipFree(p); return; }
 }
 
-// per-frame buffers whose size follows max_dets (contents do not outlive an update)
-void alloc_det_io(BoxMOTHipBotSort* h) {
-    const size_t S = h->S, nd = h->nd, dim = h->dim;
-    auto& o = h->owned;
-    if (h->reid_stream) BM_HIP(hipStreamSynchronize(h->reid_stream));
-    release(o, h->d_dets); release(o, h->d_embs); release(o, h->d_embs_alt); release(o, h->d_out);
-    release(o, h->d_crop_stream); release(o, h->d_crop_boxes); release(o, h->d_crop_row);
-    h->d_dets = zalloc<float>(S * nd * h->det_cols(), o);
-    h->d_embs = zalloc<float>(S * nd * dim, o);
-    h->d_embs_alt = zalloc<float>(S * nd * dim, o);          // step_device pipeline: frames alternate between the two tables
-    h->d_out = zalloc<float>(S * nd * h->out_cols(), o);
-    h->d_crop_stream = zalloc<int>(S * nd, o);
-    h->d_crop_boxes = zalloc<float>(S * nd * 4, o);
-    h->d_crop_row = zalloc<int>(S * nd, o);
-    release(o, h->d_cmc_boxes);
-    h->d_cmc_boxes = h->is_obb ? zalloc<float>(S * nd * 4, o) : nullptr;
-    h->h_dets.assign(S * nd * h->det_cols(), 0.f);
-    h->h_out.assign(S * nd * h->out_cols(), 0.f);
+int grown(int have, int need) {           // at least double, in steps of 64
+    int v = have * 2 > need ? have * 2 : need;
+    return (v + 63) / 64 * 64;
+}
+// Growth targets (cap, nd) for a frame that needs (need_cap, need_nd): doubled as above, but when the doubled pair exceeds what
+// `fits(cap, nd)` accepts (the assignment solver's LDS state) the sizes fall back towards the need itself in steps of 64 -- a frame
+// that fits is never refused because its DOUBLE would not.
+template <class Fits>
+void grown_pair(int have_cap, int need_cap, int have_nd, int need_nd, Fits fits, int& cap, int& nd) {
+    cap = need_cap > have_cap ? grown(have_cap, need_cap) : have_cap;
+    nd = need_nd > have_nd ? grown(have_nd, need_nd) : have_nd;
+    const int min_cap = need_cap > have_cap ? (need_cap + 63) / 64 * 64 : have_cap, min_nd = need_nd > have_nd ? (need_nd + 63) / 64 * 64 : have_nd;
+    while (!fits(cap, nd) && (cap > min_cap || nd > min_nd)) {
+        if (cap > min_cap) cap -= 64;
+        else nd -= 64;
+    }
 }
 
-// A ReID engine for S x nd crops from the handle's blob copy (read from reid_path the first time).  Returned, not installed: the
-// caller commits it together with whatever else changes size, so that a failure leaves the handle as it was.
-std::unique_ptr<bm::ReidEngine> new_reid_engine(BoxMOTHipBotSort* h, int nd) {
+struct StreamIn {
+    const float* dets; int det_rows;
+    const float* embs;
+    const uint8_t* image;
+};
+
+// ---------------------------------------------------------------------------
+// HandleCore: host plumbing shared by the BoT-SORT, DeepOCSORT and StrongSORT handles
+// ---------------------------------------------------------------------------
+// Per-frame buffers whose size follows max_dets / max_tracks (contents do not outlive an update).  The result rows are the one
+// difference between the handles: `out_rows` per stream on the device, `h_out_rows` in the host staging vector.
+void core_alloc_sized(HandleCore* h, size_t out_rows, size_t h_out_rows) {
+    auto& o = h->owned;
+    const size_t s = h->S, n = h->nd, d = h->dim;
+    if (h->reid_stream) BM_HIP(hipStreamSynchronize(h->reid_stream));       // nothing in flight reads the tables being replaced
+    release(o, h->d_dets); release(o, h->d_embs); release(o, h->d_embs_alt); release(o, h->d_out);
+    release(o, h->d_crop_stream); release(o, h->d_crop_boxes); release(o, h->d_crop_row);
+    h->d_dets = zalloc<float>(s * n * h->det_cols, o);
+    h->d_embs = zalloc<float>(s * n * d, o);
+    h->d_embs_alt = zalloc<float>(s * n * d, o);          // pipeline: frames alternate between the two tables
+    h->d_out = zalloc<float>(s * out_rows * h->out_cols, o);
+    h->d_crop_stream = zalloc<int>(s * n, o);
+    h->d_crop_boxes = zalloc<float>(s * n * 4, o);
+    h->d_crop_row = zalloc<int>(s * n, o);
+    h->h_dets.assign(s * n * h->det_cols, 0.f);
+    h->h_out.assign(h_out_rows * h->out_cols, 0.f);
+}
+
+// A ReID engine for S x nd crops from the handle's blob copy (read from reid_path the first time), as the weights configure it: the
+// caller applies its handle's preprocess / mode.  Returned, not installed: the caller commits it together with whatever else
+// changes size, so that a failure leaves the handle as it was.
+std::unique_ptr<bm::ReidEngine> core_new_reid(HandleCore* h, int nd) {
     if (h->reid_blob.empty()) h->reid_blob = bm::read_blob_file(h->reid_path.c_str());
     const long crops = (long)h->S * nd;
     std::unique_ptr<bm::ReidEngine> e(new bm::ReidEngine(h->reid_blob.data(), (long)h->reid_blob.size(), bm::reid_chunk_for(crops), (int)crops));
     if (e->feature_dim() != h->dim) throw std::runtime_error("boxmot_hip: ReID feature dim != emb_dim");
+    return e;
+}
+
+// State tables of a tracker carried over into a larger set (growth): `rec` = the new tables in allocation order, the state tables
+// first, up to `first_scratch`; every state table is [stream][slot][...], so a stream's slab only gets longer (slot ids stay
+// valid).  `tall` is the one table that holds `tall_rows` slabs per stream (BoT-SORT's per-class active lists).
+void core_migrate(HandleCore* h, const std::vector<std::pair<void*, size_t>>& rec, const void* first_scratch,
+                  const void* tall = nullptr, int tall_rows = 1) {
+    if (rec.size() != h->table_rec.size()) throw std::runtime_error("boxmot_hip: table layout changed between allocations");
+    for (size_t i = 0; i < rec.size() && rec[i].first != first_scratch; ++i) {
+        const auto& od = h->table_rec[i];
+        const size_t rows = (size_t)h->S * (tall && rec[i].first == tall ? tall_rows : 1);
+        if (od.second == rec[i].second) BM_HIP(hipMemcpy(rec[i].first, od.first, od.second, hipMemcpyDeviceToDevice));
+        else BM_HIP(hipMemcpy2D(rec[i].first, rec[i].second / rows, od.first, od.second / rows, od.second / rows, rows, hipMemcpyDeviceToDevice));
+    }
+    for (const auto& od : h->table_rec) release(h->owned, od.first);
+    h->table_rec = rec;
+}
+
+// Room for the frames of streams [s0, s0 + n) before they are staged: more detections than max_dets, or slots in use + this
+// frame's detections > max_tracks, re-makes the tables through `grow(new_cap, new_nd)` (the reference's lists have no limit; every
+// detection of a frame can become a track).  `used_on_device(s)` reads stream s's slots in use back where the host no longer
+// knows them (a device-resident step ran since the last count).
+template <class Used, class Grow, class Fits>
+void core_make_room(HandleCore* h, int s0, int n, const StreamIn* in, Used used_on_device, Grow grow, Fits fits) {
+    if (s0 < 0 || n < 1 || s0 + n > h->S) throw std::runtime_error("boxmot_hip: stream index out of range");
+    int need_nd = h->nd, need_cap = h->cap;
+    for (int k = 0; k < n; ++k) {
+        const int rows = in[k].det_rows > 0 ? in[k].det_rows : 0;
+        need_nd = rows > need_nd ? rows : need_nd;
+        if (h->h_used[s0 + k] < 0) {
+            BM_HIP(hipStreamSynchronize(h->stream));
+            h->h_used[s0 + k] = used_on_device(s0 + k);
+        }
+        need_cap = h->h_used[s0 + k] + rows > need_cap ? h->h_used[s0 + k] + rows : need_cap;
+    }
+    if (need_nd > h->nd || need_cap > h->cap) {
+        int to_cap, to_nd;
+        grown_pair(h->cap, need_cap, h->nd, need_nd, fits, to_cap, to_nd);
+        grow(to_cap, to_nd);
+    }
+}
+
+void core_set_warp(HandleCore* h, int stream, const double* warp_2x3) {
+    if (stream < 0 || stream >= h->S) throw std::runtime_error("boxmot_hip: stream index out of range");
+    if (warp_2x3 == nullptr) { h->h_warp_flag[stream] = 0; return; }
+    for (int k = 0; k < 6; ++k) {
+        if (!std::isfinite(warp_2x3[k])) throw std::runtime_error("boxmot_hip: camera-motion warp has non-finite entries");
+        h->h_warp[(size_t)stream * 6 + k] = warp_2x3[k];
+    }
+    h->h_warp_flag[stream] = 1;
+}
+
+// *_set_frame_sizes, step 1: one (rows, cols) per stream; a stream's size is fixed by its first frame or an earlier declaration, so
+// a stream that already has frames of another size is an error naming the stream.  Changes nothing.
+void core_check_frame_sizes(const HandleCore* h, const int* image_rows, const int* image_cols, int n_streams) {
+    if (!image_rows || !image_cols) throw std::runtime_error("boxmot_hip: null argument");
+    if (n_streams != h->S) throw std::runtime_error("boxmot_hip: set_frame_sizes needs one (rows, cols) per stream of the handle (" + std::to_string(h->S) + ")");
+    for (int s = 0; s < h->S; ++s) {
+        if (image_rows[s] < 1 || image_cols[s] < 1) throw std::runtime_error("boxmot_hip: stream " + std::to_string(s) + ": frame dimensions must be positive");
+        const bool seen = h->frame_bufs[s] != nullptr || !h->fs_rows.empty();
+        const int r0 = h->fs_rows.empty() ? h->frame_rows : h->fs_rows[s], c0 = h->fs_cols.empty() ? h->frame_cols : h->fs_cols[s];
+        if (seen && (r0 != image_rows[s] || c0 != image_cols[s]))
+            throw std::runtime_error("boxmot_hip: stream " + std::to_string(s) + ": frame size changed (" + std::to_string(r0) + " x " + std::to_string(c0) +
+                                     " -> " + std::to_string(image_rows[s]) + " x " + std::to_string(image_cols[s]) + ")");
+    }
+}
+// step 2: the checked sizes become the handle's, and the {W, H} table of the `_sized` crop kernels is written
+void core_commit_frame_sizes(HandleCore* h, const int* image_rows, const int* image_cols) {
+    BM_HIP(hipStreamSynchronize(h->stream));
+    if (h->reid_stream) BM_HIP(hipStreamSynchronize(h->reid_stream));
+    h->fs_rows.assign(image_rows, image_rows + h->S);
+    h->fs_cols.assign(image_cols, image_cols + h->S);
+    h->fs_mixed = false;
+    std::vector<int> dims((size_t)h->S * 2);
+    for (int s = 0; s < h->S; ++s) {
+        dims[2 * s] = image_cols[s]; dims[2 * s + 1] = image_rows[s];
+        if (image_rows[s] != image_rows[0] || image_cols[s] != image_cols[0]) h->fs_mixed = true;
+    }
+    if (!h->d_fs_dims) h->d_fs_dims = dev_alloc<int>((size_t)h->S * 2, h->owned);
+    BM_HIP(hipMemcpy(h->d_fs_dims, dims.data(), dims.size() * sizeof(int), hipMemcpyHostToDevice));
+}
+
+// The host frame of stream s into the handle's buffer of that stream (made on first use; the pointer table is re-uploaded then).
+// With per-stream sizes the buffer has that stream's declared size and the scalar arguments are not used; without, the first
+// frame fixes the one size of the handle.
+void core_upload_frame(HandleCore* h, int s, const uint8_t* image, int rows, int cols) {
+    const bool sized = !h->fs_rows.empty();
+    const size_t bytes = sized ? (size_t)h->fs_rows[s] * h->fs_cols[s] * 3 : (size_t)rows * cols * 3;
+    if (h->frame_bufs[s] == nullptr || (!sized && bytes != h->frame_bytes)) {
+        if (!sized && h->frame_bytes != 0 && bytes != h->frame_bytes) throw std::runtime_error("boxmot_hip: frame size changed between updates");
+        void* p = nullptr;
+        BM_HIP(hipMalloc(&p, bytes));
+        h->frame_bufs[s] = static_cast<uint8_t*>(p);
+        if (!sized) { h->frame_bytes = bytes; h->frame_rows = rows; h->frame_cols = cols; }
+        BM_HIP(hipMemcpy(h->d_frames, h->frame_bufs.data(), h->S * sizeof(uint8_t*), hipMemcpyHostToDevice));
+    }
+    BM_HIP(hipMemcpyAsync(h->frame_bufs[s], image, bytes, hipMemcpyHostToDevice, h->stream));
+}
+
+// the per-stream (or per-image) size table is handed to a ReID engine for one pass only
+struct FrameDimsScope { bm::ReidEngine* e; ~FrameDimsScope() { if (e) e->set_frame_dims(nullptr); } };
+
+// The crop list of streams [s0, s0 + n) -- every detection passing the confidence test (`conf > thresh`, or `>=` when inclusive)
+// -- and the ReID pass over it on stream `st`, embeddings into the rows of `d_embs` (rows of skipped detections keep stale values;
+// the step kernels never read them).  rows / cols: the one frame size (replaced by the declared sizes where there are any).
+// Where the backbone sizes its launches on the host: by `bound` when the caller declared one (>= 0; `nd_step` then receives the
+// detection counts the frame step is to read, see pad_crop_list_kernel, and `*bounded` is raised as soon as that kernel is
+// queued; returns true), else by the count read back.
+bool core_reid_pass(HandleCore* h, hipStream_t st, int s0, int n, const float* d_dets, const int* d_ndets, const uint8_t* const* d_frames,
+                    int rows, int cols, double thresh, int inclusive, float* d_embs, int bound = -1, int* nd_step = nullptr,
+                    bool* bounded = nullptr) {
+    FrameDimsScope dims_scope{h->reid.get()};
+    if (!h->fs_rows.empty()) {      // per-stream sizes: the table when they differ, else the one size as the scalars
+        rows = h->fs_rows[0]; cols = h->fs_cols[0];
+        h->reid->set_frame_dims(h->fs_mixed ? h->d_fs_dims : nullptr);
+    }
+    BM_HIP(hipMemsetAsync(h->d_crop_count, 0, 4, st));
+    hipLaunchKernelGGL(build_crop_list_kernel, dim3(n), dim3(256), 0, st, d_dets, d_ndets, h->nd, thresh,
+                       h->d_crop_count, h->d_crop_stream, h->d_crop_boxes, h->d_crop_row, s0, inclusive);
+    if (h->reid->counted_ok()) {
+        // crop count stays on the device: launches cover the capacity, surplus workgroups exit at once
+        h->reid->run_counted(d_frames, h->d_crop_stream, h->d_crop_boxes, 4, h->d_crop_count, n * h->nd, cols, rows, d_embs, h->d_crop_row, st);
+        return false;
+    }
+    if (bound >= 0) {
+        // launches sized by the caller's bound: no read-back, no stream synchronisation inside the step (the host keeps queueing)
+        const int m = bound < n * h->nd ? bound : n * h->nd;
+        // (a bound of 0 -- "no crops in this step" -- is checked like any other: one workgroup compares the count with it)
+        hipLaunchKernelGGL(pad_crop_list_kernel, dim3(m > 0 ? (m + 255) / 256 : 1), dim3(256), 0, st, (const int*)h->d_crop_count, m,
+                           h->d_crop_stream, h->d_crop_boxes, h->d_crop_row, h->d_crop_count + 1, d_ndets, nd_step, n);
+        if (bounded) *bounded = true;
+        if (m > 0) h->reid->run(d_frames, h->d_crop_stream, h->d_crop_boxes, 4, m, cols, rows, d_embs, h->d_crop_row, st);
+        return true;
+    }
+    int n_crops = 0;
+    BM_HIP(hipMemcpyAsync(&n_crops, h->d_crop_count, 4, hipMemcpyDeviceToHost, st));
+    BM_HIP(hipStreamSynchronize(st));
+    h->reid->run(d_frames, h->d_crop_stream, h->d_crop_boxes, 4, n_crops, cols, rows, d_embs, h->d_crop_row, st);
+    return false;
+}
+
+// ---- the two-stage ReID pipeline of the device-resident steps (see HandleCore) ----
+void core_pipe_create(HandleCore* h) {
+    BM_HIP(hipStreamCreate(&h->reid_stream));
+    for (int k = 0; k < 2; ++k) {
+        BM_HIP(hipEventCreateWithFlags(&h->ev_reid_done[k], hipEventDisableTiming));
+        BM_HIP(hipEventCreateWithFlags(&h->ev_embs_free[k], hipEventDisableTiming));
+    }
+    BM_HIP(hipEventCreateWithFlags(&h->ev_main, hipEventDisableTiming));
+}
+bool core_pipe_on(const HandleCore* h) { return h->pipe && h->reid_stream; }
+// the embedding table this call's ReID pass writes and its frame step reads
+float* core_pipe_table(HandleCore* h) { return (core_pipe_on(h) && h->pipe_slot) ? h->d_embs_alt : h->d_embs; }
+// stage 1: this frame's ReID goes on the returned stream -- `reid_stream`, once the step before last has finished reading the table
+// (`stream` itself without the pipeline)
+hipStream_t core_pipe_begin_reid(HandleCore* h) {
+    if (!core_pipe_on(h)) return h->stream;
+    hipStream_t rs = h->reid_stream;
+    // a host-update path used the engine / the crop list on `stream` since, or the caller holds `stream` (it may have queued the
+    // producers of this step's detections / frames there, e.g. boxmot_hip_ingest_wait): the ReID pass is ordered after `stream` --
+    // correct always; such a caller gives up the overlap, its own stream order already serialises the frames
+    if (h->engine_on_main || h->stream_exposed) {
+        BM_HIP(hipEventRecord(h->ev_main, h->stream));
+        BM_HIP(hipStreamWaitEvent(rs, h->ev_main, 0));
+        h->engine_on_main = false;
+    }
+    BM_HIP(hipStreamWaitEvent(rs, h->ev_embs_free[h->pipe_slot], 0));
+    return rs;
+}
+// the ReID pass is enqueued: the frame step on `stream` starts after it
+void core_pipe_reid_done(HandleCore* h) {
+    if (!core_pipe_on(h)) return;
+    BM_HIP(hipEventRecord(h->ev_reid_done[h->pipe_slot], h->reid_stream));
+    BM_HIP(hipStreamWaitEvent(h->stream, h->ev_reid_done[h->pipe_slot], 0));
+}
+// stage 2 enqueued (the frame step that reads this frame's embedding table is on `stream`): the table is free for the ReID pass
+// after next once that step has run
+void core_pipe_step_enqueued(HandleCore* h) {
+    if (!core_pipe_on(h)) return;
+    BM_HIP(hipEventRecord(h->ev_embs_free[h->pipe_slot], h->stream));
+    h->pipe_slot ^= 1;
+}
+
+// `rows` result rows of `oc` columns into the caller's 9-column rows (an axis-aligned row has 8: the ninth is zeroed)
+void copy_rows9(const float* src, int rows, int oc, float* dst) {
+    for (int r = 0; r < rows; ++r, dst += 9) {
+        for (int q = 0; q < oc; ++q) dst[q] = src[(size_t)r * oc + q];
+        if (oc < 9) dst[8] = 0.0f;
+    }
+}
+
+// ---------------------------------------------------------------------------
+// BoT-SORT / ByteTrack host path
+// ---------------------------------------------------------------------------
+void alloc_det_io(BoxMOTHipBotSort* h) {
+    core_alloc_sized(h, h->nd, (size_t)h->S * h->nd);
+    release(h->owned, h->d_cmc_boxes);
+    h->d_cmc_boxes = h->is_obb ? zalloc<float>((size_t)h->S * h->nd * 4, h->owned) : nullptr;
+}
+
+std::unique_ptr<bm::ReidEngine> new_reid_engine(BoxMOTHipBotSort* h, int nd) {
+    std::unique_ptr<bm::ReidEngine> e = core_new_reid(h, nd);
     e->set_preprocess(h->reid_pad);
     if (h->reid_mode) e->set_mode(h->reid_mode);
     return e;
 }
-void make_reid_engine(BoxMOTHipBotSort* h) { h->reid = new_reid_engine(h, h->nd); }
 
 void set_step_lds(BoxMOTHipBotSort* h) {
     const long lds = bm::lap_lds_bytes(h->cap, h->nd);
@@ -601,15 +795,7 @@ void grow_tables(BoxMOTHipBotSort* h, int new_cap, int new_nd) {
     RecAlloc ra{&h->owned, &rec};
     bm::BotSortSizes z{h->S, new_cap, new_nd, h->dim, h->n_lists, h->args.st.removed_alloc, h->is_obb ? 1 : 0};
     bm::botsort_allocate(na, z, ra);
-    if (rec.size() != h->table_rec.size()) throw std::runtime_error("boxmot_hip: table layout changed between allocations");
-    for (size_t i = 0; i < rec.size() && rec[i].first != (void*)na.sc.det_xywh; ++i) {          // the state tables come first
-        const auto& od = h->table_rec[i];
-        const size_t rows = (size_t)h->S * (rec[i].first == (void*)na.st.active_list ? h->n_lists : 1);
-        if (od.second == rec[i].second) BM_HIP(hipMemcpy(rec[i].first, od.first, od.second, hipMemcpyDeviceToDevice));
-        else BM_HIP(hipMemcpy2D(rec[i].first, rec[i].second / rows, od.first, od.second / rows, od.second / rows, rows, hipMemcpyDeviceToDevice));
-    }
-    for (const auto& od : h->table_rec) release(h->owned, od.first);
-    h->table_rec = rec;
+    core_migrate(h, rec, na.sc.det_xywh, na.st.active_list, h->n_lists);          // the state tables come first
     h->args = na;
     const bool more_dets = new_nd != h->nd;
     h->cap = new_cap; h->nd = new_nd;
@@ -619,24 +805,6 @@ void grow_tables(BoxMOTHipBotSort* h, int new_cap, int new_nd) {
     }
     set_step_lds(h);
     ++h->n_grows;
-}
-
-int grown(int have, int need) {           // at least double, in steps of 64
-    int v = have * 2 > need ? have * 2 : need;
-    return (v + 63) / 64 * 64;
-}
-// Growth targets (cap, nd) for a frame that needs (need_cap, need_nd): doubled as above, but when the doubled pair exceeds what
-// `fits(cap, nd)` accepts (the assignment solver's LDS state) the sizes fall back towards the need itself in steps of 64 -- a frame
-// that fits is never refused because its DOUBLE would not.
-template <class Fits>
-void grown_pair(int have_cap, int need_cap, int have_nd, int need_nd, Fits fits, int& cap, int& nd) {
-    cap = need_cap > have_cap ? grown(have_cap, need_cap) : have_cap;
-    nd = need_nd > have_nd ? grown(have_nd, need_nd) : have_nd;
-    const int min_cap = need_cap > have_cap ? (need_cap + 63) / 64 * 64 : have_cap, min_nd = need_nd > have_nd ? (need_nd + 63) / 64 * 64 : have_nd;
-    while (!fits(cap, nd) && (cap > min_cap || nd > min_nd)) {
-        if (cap > min_cap) cap -= 64;
-        else nd -= 64;
-    }
 }
 
 void zero_state(BoxMOTHipBotSort* h) {
@@ -677,6 +845,7 @@ void build(BoxMOTHipBotSort* h) {
         h->cfg.with_reid = 0; h->cfg.fuse_first_associate = 1;
     }
     h->is_obb = c.is_obb != 0;
+    if (h->is_obb) { h->det_cols = bm::obb::DET_COLS; h->out_cols = bm::obb::OUT_COLS; }
     if (h->is_obb) {
         // oriented detections (botsort.py:120-131, bytetrack.py:266-303).  Camera motion: a warp supplied with set_warp is applied to
         // the oriented tracks (STrack.multi_gmc_obb, botsort_track.py:197-230: kf_warp_wave of the oriented layout); the in-handle
@@ -698,14 +867,7 @@ void build(BoxMOTHipBotSort* h) {
         int cus = 0, dev = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
         h->pipe = (v && v[0]) ? v[0] != '0' : 2 * c.n_streams <= cus;
-        if (h->pipe && !h->reid_stream) {
-            BM_HIP(hipStreamCreate(&h->reid_stream));
-            for (int k = 0; k < 2; ++k) {
-                BM_HIP(hipEventCreateWithFlags(&h->ev_reid_done[k], hipEventDisableTiming));
-                BM_HIP(hipEventCreateWithFlags(&h->ev_embs_free[k], hipEventDisableTiming));
-            }
-            BM_HIP(hipEventCreateWithFlags(&h->ev_main, hipEventDisableTiming));
-        }
+        if (h->pipe && !h->reid_stream) core_pipe_create(h);
     }
     BM_HIP(hipEventCreate(&h->ev[0]));
     BM_HIP(hipEventCreate(&h->ev[1]));
@@ -740,7 +902,7 @@ void build(BoxMOTHipBotSort* h) {
         throw std::runtime_error("boxmot_hip: max_tracks/max_dets too large for the assignment solver's LDS state");
     set_step_lds(h);
     (void)cap; (void)nd; (void)dim;
-    if (c.with_reid && !h->reid_path.empty()) make_reid_engine(h);
+    if (c.with_reid && !h->reid_path.empty()) h->reid = new_reid_engine(h, h->nd);
 }
 
 void launch_step(BoxMOTHipBotSort* h, int s0, int n_streams, const float* d_dets, const int* d_ndets, const float* d_embs,
@@ -774,29 +936,13 @@ void launch_step(BoxMOTHipBotSort* h, int s0, int n_streams, const float* d_dets
     BM_HIP(hipGetLastError());
 }
 
-// ReID for every high-confidence detection of the first n_streams streams; writes d_embs rows.
-void run_reid(BoxMOTHipBotSort* h, int s0, int n_streams, const float* d_dets, const int* d_ndets,
-              const uint8_t* const* d_frames, int rows, int cols, float* d_embs, hipStream_t st = nullptr) {
+// ReID on stream `st` for every detection above track_high_thresh (botsort.py:191-192, :260) of streams [s0, s0 + n_streams);
+// writes d_embs rows
+void run_reid(BoxMOTHipBotSort* h, hipStream_t st, int s0, int n_streams, const float* d_dets, const int* d_ndets,
+              const uint8_t* const* d_frames, int rows, int cols, float* d_embs) {
     if (!h->reid) throw std::runtime_error("boxmot_hip: with_reid=1 and no embeddings supplied, but no ReID weights are loaded");
-    if (!st) { st = h->stream; h->engine_on_main = true; }
-    struct DimsScope { bm::ReidEngine* e; ~DimsScope() { e->set_frame_dims(nullptr); } } dims_scope{h->reid.get()};
-    if (!h->fs_rows.empty()) {      // per-stream sizes: the table when they differ, else the one size as the scalars (the launches of today)
-        rows = h->fs_rows[0]; cols = h->fs_cols[0];
-        h->reid->set_frame_dims(h->fs_mixed ? h->d_fs_dims : nullptr);
-    }
-    BM_HIP(hipMemsetAsync(h->d_crop_count, 0, 4, st));
-    hipLaunchKernelGGL(build_crop_list_kernel, dim3(n_streams), dim3(256), 0, st, d_dets, d_ndets, h->nd,
-                       h->cfg.track_high_thresh, h->d_crop_count, h->d_crop_stream, h->d_crop_boxes, h->d_crop_row, s0);
-    if (h->reid->counted_ok()) {
-        // crop count stays on the device: launches cover the capacity, surplus workgroups exit at once
-        h->reid->run_counted(d_frames, h->d_crop_stream, h->d_crop_boxes, 4, h->d_crop_count, n_streams * h->nd, cols, rows,
-                             d_embs, h->d_crop_row, st);
-        return;
-    }
-    int n_crops = 0;
-    BM_HIP(hipMemcpyAsync(&n_crops, h->d_crop_count, 4, hipMemcpyDeviceToHost, st));
-    BM_HIP(hipStreamSynchronize(st));
-    h->reid->run(d_frames, h->d_crop_stream, h->d_crop_boxes, 4, n_crops, cols, rows, d_embs, h->d_crop_row, st);
+    if (st == h->stream) h->engine_on_main = true;
+    core_reid_pass(h, st, s0, n_streams, d_dets, d_ndets, d_frames, rows, cols, h->cfg.track_high_thresh, 0, d_embs);
 }
 
 // Status words of streams [s0, s0 + n): a non-zero word is reported once and cleared, so that one overflow neither poisons the
@@ -822,32 +968,6 @@ std::string take_status(hipStream_t stream, int* d_status, int s0, int n, const 
         BM_HIP(hipStreamSynchronize(stream));
     }
     return msg;
-}
-
-void upload_frame(BoxMOTHipBotSort* h, int s, const uint8_t* image, int rows, int cols, int channels) {
-    if (channels != 3) throw std::runtime_error("boxmot_hip: ReID needs a 3-channel uint8 BGR image");
-    if (!h->fs_rows.empty()) {      // per-stream sizes: one buffer per stream of that stream's size (the scalar arguments are not used)
-        const size_t sbytes = (size_t)h->fs_rows[s] * h->fs_cols[s] * 3;
-        if (h->frame_bufs[s] == nullptr) {
-            void* p = nullptr;
-            BM_HIP(hipMalloc(&p, sbytes));
-            h->frame_bufs[s] = static_cast<uint8_t*>(p);
-            BM_HIP(hipMemcpy(h->d_frames, h->frame_bufs.data(), h->S * sizeof(uint8_t*), hipMemcpyHostToDevice));
-        }
-        BM_HIP(hipMemcpyAsync(h->frame_bufs[s], image, sbytes, hipMemcpyHostToDevice, h->stream));
-        return;
-    }
-    const size_t bytes = (size_t)rows * cols * 3;
-    if (h->frame_bufs[s] == nullptr || bytes != h->frame_bytes) {
-        if (h->frame_bytes != 0 && bytes != h->frame_bytes)
-            throw std::runtime_error("boxmot_hip: frame size changed between updates");
-        void* p = nullptr;
-        BM_HIP(hipMalloc(&p, bytes));
-        h->frame_bufs[s] = static_cast<uint8_t*>(p);
-        h->frame_bytes = bytes; h->frame_rows = rows; h->frame_cols = cols;
-        BM_HIP(hipMemcpy(h->d_frames, h->frame_bufs.data(), h->S * sizeof(uint8_t*), hipMemcpyHostToDevice));
-    }
-    BM_HIP(hipMemcpyAsync(h->frame_bufs[s], image, bytes, hipMemcpyHostToDevice, h->stream));
 }
 
 // ---- ECC estimator plumbing (C ABI boxmot_hip_ecc_*; also owned by a BoT-SORT handle created with cmc_method = "ecc") ----
@@ -970,12 +1090,6 @@ void sof_stage_dets(BoxMOTHipSof* h, int stream, const float* dets, int n_dets, 
     BM_HIP(hipStreamSynchronize(h->stream));            // rows / n_dets are stack and local storage
 }
 
-struct StreamIn {
-    const float* dets; int det_rows;
-    const float* embs;
-    const uint8_t* image;
-};
-
 // The estimator that owns stream s: the handle's one estimator (one frame size per handle, from the call's arguments), or -- with
 // per-stream sizes -- the estimator of that stream's size, made when a stream of the size is first estimated.
 BoxMOTHipSof* sof_of(BoxMOTHipBotSort* h, int s, int image_rows, int image_cols) {
@@ -1009,31 +1123,16 @@ BoxMOTHipEcc* ecc_of(BoxMOTHipBotSort* h, int s, int image_rows, int image_cols)
 void host_update(BoxMOTHipBotSort* h, int s0, int n, const StreamIn* in, int det_cols, int emb_cols,
                  int image_rows, int image_cols, int image_channels, const int* list_sel, const int* fc_set,
                  float* const* out, int out_capacity_rows, int* out_rows, const uint8_t* const* d_frames_ext = nullptr) {
-    {   // the reference has no capacities: make room before the step (every detection of a frame can become a track)
-        int need_nd = h->nd, need_cap = h->cap;
-        for (int k = 0; k < n; ++k) {
-            const int rows = in[k].det_rows > 0 ? in[k].det_rows : 0;
-            need_nd = rows > need_nd ? rows : need_nd;
-            if (h->h_used[s0 + k] < 0) {                   // a device-resident step ran since the last count: ask the device
-                const bm::BotSortState& st = h->args.st;
-                std::vector<int> cnt(h->n_lists + 1);
-                BM_HIP(hipStreamSynchronize(h->stream));
-                BM_HIP(hipMemcpy(cnt.data(), st.n_active + (size_t)(s0 + k) * h->n_lists, h->n_lists * 4, hipMemcpyDeviceToHost));
-                BM_HIP(hipMemcpy(cnt.data() + h->n_lists, st.n_lost + s0 + k, 4, hipMemcpyDeviceToHost));
-                int used = 0;
-                for (int v : cnt) used += v;
-                h->h_used[s0 + k] = used;
-            }
-            need_cap = h->h_used[s0 + k] + rows > need_cap ? h->h_used[s0 + k] + rows : need_cap;
-        }
-        if (need_nd > h->nd || need_cap > h->cap) {
-            int to_cap, to_nd;
-            grown_pair(h->cap, need_cap, h->nd, need_nd, [](int c, int d) { return bm::lap_lds_bytes(c, d) <= 120 * 1024; }, to_cap, to_nd);
-            grow_tables(h, to_cap, to_nd);
-        }
-    }
+    core_make_room(h, s0, n, in, [&](int s) {       // slots in use = tracked + lost tracks (removed ones give their slot back)
+        std::vector<int> cnt(h->n_lists + 1);
+        BM_HIP(hipMemcpy(cnt.data(), h->args.st.n_active + (size_t)s * h->n_lists, h->n_lists * 4, hipMemcpyDeviceToHost));
+        BM_HIP(hipMemcpy(cnt.data() + h->n_lists, h->args.st.n_lost + s, 4, hipMemcpyDeviceToHost));
+        int used = 0;
+        for (int v : cnt) used += v;
+        return used;
+    }, [&](int cap, int nd) { grow_tables(h, cap, nd); }, [](int c, int d) { return bm::lap_lds_bytes(c, d) <= 120 * 1024; });
     const int nd = h->nd, dim = h->dim;
-    const int DC = h->det_cols(), OC = h->out_cols();
+    const int DC = h->det_cols, OC = h->out_cols;
     bool need_reid = false;
     for (int k = 0; k < n; ++k) {
         const int rows = in[k].det_rows;
@@ -1077,7 +1176,7 @@ void host_update(BoxMOTHipBotSort* h, int s0, int n, const StreamIn* in, int det
             if (in[k].det_rows < 0) continue;
             if (!in[k].image && !d_frames_ext) throw std::runtime_error("boxmot_hip: cmc_method=sof needs the frame (image pointer is null)");
             if (image_channels != 3) throw std::runtime_error("boxmot_hip: cmc_method=sof needs a 3-channel uint8 BGR image");
-            if (!d_frames_ext) upload_frame(h, s0 + k, in[k].image, image_rows, image_cols, image_channels);
+            if (!d_frames_ext) core_upload_frame(h, s0 + k, in[k].image, image_rows, image_cols);
         }
         for (int k = 0; k < n; ++k) {
             if (in[k].det_rows < 0) continue;
@@ -1102,7 +1201,7 @@ void host_update(BoxMOTHipBotSort* h, int s0, int n, const StreamIn* in, int det
             if (in[k].det_rows < 0) continue;
             if (!in[k].image) throw std::runtime_error("boxmot_hip: cmc_method=ecc needs the frame (image pointer is null)");
             if (image_channels != 3) throw std::runtime_error("boxmot_hip: cmc_method=ecc needs a 3-channel uint8 BGR image");
-            if (!d_frames_ext) upload_frame(h, s0 + k, in[k].image, image_rows, image_cols, image_channels);
+            if (!d_frames_ext) core_upload_frame(h, s0 + k, in[k].image, image_rows, image_cols);
         }
         for (int k = 0; k < n; ++k) {
             if (in[k].det_rows < 0) continue;
@@ -1125,13 +1224,15 @@ void host_update(BoxMOTHipBotSort* h, int s0, int n, const StreamIn* in, int det
     h->last_reid_pre_ms = h->last_reid_proc_ms = 0;
     if (need_reid && d_frames_ext) {       // frames already on the device (ingest ring slot): no upload
         if (s0 != 0) throw std::runtime_error("boxmot_hip: device frames are addressed from stream 0");
-        run_reid(h, s0, n, h->d_dets, h->d_ndets, d_frames_ext, image_rows, image_cols, h->d_embs);
+        run_reid(h, h->stream, s0, n, h->d_dets, h->d_ndets, d_frames_ext, image_rows, image_cols, h->d_embs);
     } else if (need_reid) {
         for (int k = 0; k < n; ++k) {
-            if (in[k].image) { if (!ecc_here) upload_frame(h, s0 + k, in[k].image, image_rows, image_cols, image_channels); }
-            else if (h->frame_bufs[s0 + k] == nullptr) throw std::runtime_error("Image data pointer is null.");
+            if (in[k].image && !ecc_here) {
+                if (image_channels != 3) throw std::runtime_error("boxmot_hip: ReID needs a 3-channel uint8 BGR image");
+                core_upload_frame(h, s0 + k, in[k].image, image_rows, image_cols);
+            } else if (!in[k].image && h->frame_bufs[s0 + k] == nullptr) throw std::runtime_error("Image data pointer is null.");
         }
-        run_reid(h, s0, n, h->d_dets, h->d_ndets, h->d_frames, h->frame_rows, h->frame_cols, h->d_embs);
+        run_reid(h, h->stream, s0, n, h->d_dets, h->d_ndets, h->d_frames, h->frame_rows, h->frame_cols, h->d_embs);
     }
     BM_HIP(hipEventRecord(h->ev[0], h->stream));
     launch_step(h, s0, n, h->d_dets, h->d_ndets, h->cfg.with_reid ? h->d_embs : nullptr, h->d_list_sel,
@@ -1157,12 +1258,7 @@ void host_update(BoxMOTHipBotSort* h, int s0, int n, const StreamIn* in, int det
     for (int k = 0; k < n; ++k) {
         const int rows = h->h_out_n[k];
         if (rows > out_capacity_rows) throw std::runtime_error("boxmot_hip: output buffer is too small for the current frame.");
-        const float* src = h->h_out.data() + (size_t)k * nd * OC;
-        for (int r = 0; r < rows; ++r) {
-            float* dst = out[k] + (size_t)r * 9;
-            for (int q = 0; q < OC; ++q) dst[q] = src[r * OC + q];
-            if (OC < 9) dst[8] = 0.0f;
-        }
+        copy_rows9(h->h_out.data() + (size_t)k * nd * OC, rows, OC, out[k]);
         out_rows[k] = rows;
     }
     if (!status_msg.empty()) throw std::runtime_error(status_msg);      // rows of this frame are in `out` all the same
@@ -1186,31 +1282,9 @@ void host_update_one(BoxMOTHipBotSort* h, int stream, int class_list, int frame_
 // StreamIo: shared host plumbing of the DeepOCSORT / StrongSORT handles
 // ---------------------------------------------------------------------------
 std::unique_ptr<bm::ReidEngine> io_new_reid(StreamIo* h, int nd) {
-    if (h->reid_blob.empty()) h->reid_blob = bm::read_blob_file(h->reid_path.c_str());
-    const long crops = (long)h->S * nd;
-    std::unique_ptr<bm::ReidEngine> e(new bm::ReidEngine(h->reid_blob.data(), (long)h->reid_blob.size(), bm::reid_chunk_for(crops), (int)crops));
-    if (e->feature_dim() != h->dim) throw std::runtime_error("boxmot_hip: ReID feature dim != emb_dim");
+    std::unique_ptr<bm::ReidEngine> e = core_new_reid(h, nd);
     if (h->reid_mode >= 0) e->set_mode(h->reid_mode);
     return e;
-}
-void io_make_reid(StreamIo* h) { h->reid = io_new_reid(h, h->nd); }
-
-// per-frame buffers whose size follows max_dets / max_tracks (contents do not outlive an update)
-void io_alloc_sized(StreamIo* h) {
-    auto& o = h->owned;
-    const size_t s = h->S, c = h->cap, n = h->nd, d = h->dim;
-    if (h->reid_stream) BM_HIP(hipStreamSynchronize(h->reid_stream));       // nothing in flight reads the tables being replaced
-    release(o, h->d_dets); release(o, h->d_embs); release(o, h->d_embs_alt); release(o, h->d_out);
-    release(o, h->d_crop_stream); release(o, h->d_crop_boxes); release(o, h->d_crop_row);
-    h->d_dets = zalloc<float>(s * n * h->det_cols, o);
-    h->d_embs = zalloc<float>(s * n * d, o);
-    h->d_embs_alt = zalloc<float>(s * n * d, o);          // step_device_frames pipeline: frames alternate between the two tables
-    h->d_out = zalloc<float>(s * c * h->out_cols, o);
-    h->d_crop_stream = zalloc<int>(s * n, o);
-    h->d_crop_boxes = zalloc<float>(s * n * 4, o);
-    h->d_crop_row = zalloc<int>(s * n, o);
-    h->h_dets.assign(s * n * h->det_cols, 0.f);
-    h->h_out.assign(c * h->out_cols, 0.f);
 }
 
 void io_allocate(StreamIo* h, int S, int cap, int nd, int dim, bool with_reid) {
@@ -1219,18 +1293,11 @@ void io_allocate(StreamIo* h, int S, int cap, int nd, int dim, bool with_reid) {
     {
         const char* v = std::getenv("BOXMOT_HIP_PIPELINE");
         h->pipe = !(v && v[0] == '0');
-        if (h->pipe) {
-            BM_HIP(hipStreamCreate(&h->reid_stream));
-            for (int k = 0; k < 2; ++k) {
-                BM_HIP(hipEventCreateWithFlags(&h->ev_reid_done[k], hipEventDisableTiming));
-                BM_HIP(hipEventCreateWithFlags(&h->ev_embs_free[k], hipEventDisableTiming));
-            }
-            BM_HIP(hipEventCreateWithFlags(&h->ev_main, hipEventDisableTiming));
-        }
+        if (h->pipe) core_pipe_create(h);
     }
     auto& o = h->owned;
     const size_t s = S;
-    io_alloc_sized(h);
+    core_alloc_sized(h, h->cap, h->cap);        // result rows: [S][cap] on the device, one stream's at a time on the host
     h->d_ndets = zalloc<int>(s, o);
     h->d_out_n = zalloc<int>(s, o);
     h->d_warp = zalloc<double>(s * 6, o);
@@ -1241,55 +1308,16 @@ void io_allocate(StreamIo* h, int S, int cap, int nd, int dim, bool with_reid) {
     h->d_frames = zalloc<const uint8_t*>(s, o);
     h->d_crop_count = zalloc<int>(2, o);        // [0] the count, [1] the bound-overflow flag
     h->d_ndets_step[0] = zalloc<int>(s, o); h->d_ndets_step[1] = zalloc<int>(s, o);
-    if (with_reid && !h->reid_path.empty()) io_make_reid(h);
+    if (with_reid && !h->reid_path.empty()) h->reid = io_new_reid(h, h->nd);
 }
 
-// State tables of a tracker carried over into a larger set (see grow_tables): `rec` = the new tables in allocation order, the
-// state tables first, up to `first_scratch`; every state table is [stream][slot][...], so a stream's slab only gets longer.
-void io_migrate(StreamIo* h, const std::vector<std::pair<void*, size_t>>& rec, const void* first_scratch) {
-    if (rec.size() != h->table_rec.size()) throw std::runtime_error("boxmot_hip: table layout changed between allocations");
-    const size_t rows = (size_t)h->S;
-    for (size_t i = 0; i < rec.size() && rec[i].first != first_scratch; ++i) {
-        const auto& od = h->table_rec[i];
-        if (od.second == rec[i].second) BM_HIP(hipMemcpy(rec[i].first, od.first, od.second, hipMemcpyDeviceToDevice));
-        else BM_HIP(hipMemcpy2D(rec[i].first, rec[i].second / rows, od.first, od.second / rows, od.second / rows, rows, hipMemcpyDeviceToDevice));
-    }
-    for (const auto& od : h->table_rec) release(h->owned, od.first);
-    h->table_rec = rec;
-}
-
-// Room for the frames of streams [s0, s0 + n) before they are staged: more detections than max_dets, or live tracks + this
-// frame's detections > max_tracks, re-makes the tables through `grow(new_cap, new_nd)` (the reference's lists have no limit).
+// core_make_room for these handles: the slots in use are the tracker's n_tracks word, and the stream is drained before the tables
+// are re-made
 template <class Grow, class Fits>
 void io_make_room(StreamIo* h, int s0, int n, const StreamIn* in, const int* d_n_tracks, Grow grow, Fits fits) {
-    if (s0 < 0 || n < 1 || s0 + n > h->S) throw std::runtime_error("boxmot_hip: stream index out of range");
-    int need_nd = h->nd, need_cap = h->cap;
-    for (int k = 0; k < n; ++k) {
-        const int rows = in[k].det_rows > 0 ? in[k].det_rows : 0;
-        need_nd = rows > need_nd ? rows : need_nd;
-        if (h->h_used[s0 + k] < 0) {
-            BM_HIP(hipStreamSynchronize(h->stream));
-            BM_HIP(hipMemcpy(&h->h_used[s0 + k], d_n_tracks + s0 + k, 4, hipMemcpyDeviceToHost));
-        }
-        need_cap = h->h_used[s0 + k] + rows > need_cap ? h->h_used[s0 + k] + rows : need_cap;
-    }
-    if (need_nd > h->nd || need_cap > h->cap) {
-        BM_HIP(hipStreamSynchronize(h->stream));
-        int to_cap, to_nd;
-        grown_pair(h->cap, need_cap, h->nd, need_nd, fits, to_cap, to_nd);
-        grow(to_cap, to_nd);
-        ++h->n_grows;
-    }
-}
-
-void io_set_warp(StreamIo* h, int stream, const double* warp_2x3) {
-    if (stream < 0 || stream >= h->S) throw std::runtime_error("boxmot_hip: stream index out of range");
-    if (warp_2x3 == nullptr) { h->h_warp_flag[stream] = 0; return; }
-    for (int k = 0; k < 6; ++k) {
-        if (!std::isfinite(warp_2x3[k])) throw std::runtime_error("boxmot_hip: camera-motion warp has non-finite entries");
-        h->h_warp[(size_t)stream * 6 + k] = warp_2x3[k];
-    }
-    h->h_warp_flag[stream] = 1;
+    core_make_room(h, s0, n, in,
+                   [&](int s) { int used = 0; BM_HIP(hipMemcpy(&used, d_n_tracks + s, 4, hipMemcpyDeviceToHost)); return used; },
+                   [&](int cap, int nd) { BM_HIP(hipStreamSynchronize(h->stream)); grow(cap, nd); }, fits);
 }
 
 // Device-resident steps: the warps set with *_set_warp since the last step are consumed by this one (identity for the streams
@@ -1314,36 +1342,6 @@ bool io_consume_warps(StreamIo* h) {
 }
 // after a device-resident step: pending warps are consumed, and the host no longer knows the track counts (io_make_room asks)
 void io_clear_warps(StreamIo* h) { for (int s = 0; s < h->S; ++s) { h->h_warp_flag[s] = 0; h->h_used[s] = -1; } }
-
-// the per-stream size table is handed to the engine for one pass only
-struct IoDimsScope { bm::ReidEngine* e; ~IoDimsScope() { if (e) e->set_frame_dims(nullptr); } };
-
-// boxmot_hip_{deepocsort,strongsort}_set_frame_sizes: one (rows, cols) per stream; a stream that already has frames of another size
-// is an error naming the stream
-void io_set_frame_sizes(StreamIo* h, const int* image_rows, const int* image_cols, int n_streams) {
-    if (!image_rows || !image_cols) throw std::runtime_error("boxmot_hip: null argument");
-    if (n_streams != h->S) throw std::runtime_error("boxmot_hip: set_frame_sizes needs one (rows, cols) per stream of the handle (" + std::to_string(h->S) + ")");
-    for (int s = 0; s < h->S; ++s) {
-        if (image_rows[s] < 1 || image_cols[s] < 1) throw std::runtime_error("boxmot_hip: stream " + std::to_string(s) + ": frame dimensions must be positive");
-        const bool seen = h->frame_bufs[s] != nullptr || !h->fs_rows.empty();
-        const int r0 = h->fs_rows.empty() ? h->frame_rows : h->fs_rows[s], c0 = h->fs_cols.empty() ? h->frame_cols : h->fs_cols[s];
-        if (seen && (r0 != image_rows[s] || c0 != image_cols[s]))
-            throw std::runtime_error("boxmot_hip: stream " + std::to_string(s) + ": frame size changed (" + std::to_string(r0) + " x " + std::to_string(c0) +
-                                     " -> " + std::to_string(image_rows[s]) + " x " + std::to_string(image_cols[s]) + ")");
-    }
-    BM_HIP(hipStreamSynchronize(h->stream));
-    if (h->reid_stream) BM_HIP(hipStreamSynchronize(h->reid_stream));
-    h->fs_rows.assign(image_rows, image_rows + h->S);
-    h->fs_cols.assign(image_cols, image_cols + h->S);
-    h->fs_mixed = false;
-    std::vector<int> dims((size_t)h->S * 2);
-    for (int s = 0; s < h->S; ++s) {
-        dims[2 * s] = image_cols[s]; dims[2 * s + 1] = image_rows[s];
-        if (image_rows[s] != image_rows[0] || image_cols[s] != image_cols[0]) h->fs_mixed = true;
-    }
-    if (!h->d_fs_dims) h->d_fs_dims = dev_alloc<int>((size_t)h->S * 2, h->owned);
-    BM_HIP(hipMemcpy(h->d_fs_dims, dims.data(), dims.size() * sizeof(int), hipMemcpyHostToDevice));
-}
 
 // Validate and upload the inputs of the first n streams; run the ReID engine on every detection passing the confidence
 // test (`conf > thresh`, or `>=` when inclusive) when embeddings are wanted and not supplied.  Streams without a pending
@@ -1395,48 +1393,12 @@ bool io_stage(StreamIo* h, int n, const StreamIn* in, int det_cols, int emb_cols
     if (!need_reid) return any_warp;
     if (!h->reid) throw std::runtime_error("boxmot_hip: embeddings are needed and none were supplied, but no ReID weights are loaded");
     if (image_channels != 3) throw std::runtime_error("boxmot_hip: ReID needs a 3-channel uint8 BGR image");
-    const size_t bytes = (size_t)image_rows * image_cols * 3;
-    const bool sized = !h->fs_rows.empty();
     for (int k = 0; k < n; ++k) {
-        const int sk = s0 + k;
-        if (!in[k].image) { if (!h->frame_bufs[sk]) throw std::runtime_error("Image data pointer is null."); continue; }
-        if (sized) {        // one buffer per stream of that stream's size (the scalar arguments are not used)
-            const size_t sbytes = (size_t)h->fs_rows[sk] * h->fs_cols[sk] * 3;
-            if (h->frame_bufs[sk] == nullptr) {
-                void* p = nullptr;
-                BM_HIP(hipMalloc(&p, sbytes));
-                h->frame_bufs[sk] = static_cast<uint8_t*>(p);
-                BM_HIP(hipMemcpy(h->d_frames, h->frame_bufs.data(), h->S * sizeof(uint8_t*), hipMemcpyHostToDevice));
-            }
-            BM_HIP(hipMemcpyAsync(h->frame_bufs[sk], in[k].image, sbytes, hipMemcpyHostToDevice, h->stream));
-            continue;
-        }
-        if (h->frame_bufs[sk] == nullptr || bytes != h->frame_bytes) {
-            if (h->frame_bytes != 0 && bytes != h->frame_bytes) throw std::runtime_error("boxmot_hip: frame size changed between updates");
-            void* p = nullptr;
-            BM_HIP(hipMalloc(&p, bytes));
-            h->frame_bufs[sk] = static_cast<uint8_t*>(p);
-            h->frame_bytes = bytes; h->frame_rows = image_rows; h->frame_cols = image_cols;
-            BM_HIP(hipMemcpy(h->d_frames, h->frame_bufs.data(), h->S * sizeof(uint8_t*), hipMemcpyHostToDevice));
-        }
-        BM_HIP(hipMemcpyAsync(h->frame_bufs[sk], in[k].image, bytes, hipMemcpyHostToDevice, h->stream));
+        if (in[k].image) core_upload_frame(h, s0 + k, in[k].image, image_rows, image_cols);
+        else if (!h->frame_bufs[s0 + k]) throw std::runtime_error("Image data pointer is null.");
     }
     h->engine_on_main = true;           // (a later pipelined step_device_frames orders its ReID pass after this use)
-    IoDimsScope dims_scope{h->reid.get()};
-    if (sized) { h->frame_rows = h->fs_rows[0]; h->frame_cols = h->fs_cols[0]; h->reid->set_frame_dims(h->fs_mixed ? h->d_fs_dims : nullptr); }
-    BM_HIP(hipMemsetAsync(h->d_crop_count, 0, 4, h->stream));
-    hipLaunchKernelGGL(build_crop_list_kernel, dim3(n), dim3(256), 0, h->stream, h->d_dets, h->d_ndets, nd, reid_thresh,
-                       h->d_crop_count, h->d_crop_stream, h->d_crop_boxes, h->d_crop_row, s0, inclusive);
-    if (h->reid->counted_ok()) {
-        h->reid->run_counted(h->d_frames, h->d_crop_stream, h->d_crop_boxes, 4, h->d_crop_count, n * nd, h->frame_cols,
-                             h->frame_rows, h->d_embs, h->d_crop_row, h->stream);
-    } else {
-        int n_crops = 0;
-        BM_HIP(hipMemcpyAsync(&n_crops, h->d_crop_count, 4, hipMemcpyDeviceToHost, h->stream));
-        BM_HIP(hipStreamSynchronize(h->stream));
-        h->reid->run(h->d_frames, h->d_crop_stream, h->d_crop_boxes, 4, n_crops, h->frame_cols, h->frame_rows, h->d_embs,
-                     h->d_crop_row, h->stream);
-    }
+    core_reid_pass(h, h->stream, s0, n, h->d_dets, h->d_ndets, h->d_frames, h->frame_rows, h->frame_cols, reid_thresh, inclusive, h->d_embs);
     return any_warp;
 }
 
@@ -1446,60 +1408,17 @@ bool io_stage(StreamIo* h, int n, const StreamIn* in, int det_cols, int emb_cols
 float* io_device_reid(StreamIo* h, const float* d_dets, const int* d_ndets, const uint8_t* const* d_frames, int image_rows,
                       int image_cols, double reid_thresh, int inclusive) {
     if (!h->reid) throw std::runtime_error("boxmot_hip: embeddings are needed and none were supplied, but no ReID weights are loaded");
-    const bool sized = !h->fs_rows.empty();
-    if (!d_frames || (!sized && (image_rows <= 0 || image_cols <= 0))) throw std::runtime_error("boxmot_hip: step_device_frames needs device frames");
-    IoDimsScope dims_scope{h->reid.get()};
-    if (sized) { image_rows = h->fs_rows[0]; image_cols = h->fs_cols[0]; h->reid->set_frame_dims(h->fs_mixed ? h->d_fs_dims : nullptr); }
-    // pipeline stage 1 (StreamIo): this frame's ReID on `reid_stream`, into the table the step before last has finished reading
-    const bool pipe = h->pipe && h->reid_stream;
-    hipStream_t rs = pipe ? h->reid_stream : h->stream;
-    float* embs = (pipe && h->pipe_slot) ? h->d_embs_alt : h->d_embs;
+    if (!d_frames || (h->fs_rows.empty() && (image_rows <= 0 || image_cols <= 0))) throw std::runtime_error("boxmot_hip: step_device_frames needs device frames");
+    // pipeline stage 1: this frame's ReID on `reid_stream`, into the table the step before last has finished reading
+    hipStream_t rs = core_pipe_begin_reid(h);
+    float* embs = core_pipe_table(h);
+    int* nd_step = h->d_ndets_step[core_pipe_on(h) ? h->pipe_slot : 0];        // (alternates with the embedding table: read by this call's step)
     h->step_ndets = d_ndets;
-    if (pipe) {
-        // a host-update path used the engine / the crop list on `stream` since, or the caller holds `stream` (it may have queued the
-        // producers of this step's detections / frames there, e.g. boxmot_hip_ingest_wait): the ReID pass is ordered after `stream` --
-        // correct always; such a caller gives up the overlap, its own stream order already serialises the frames
-        if (h->engine_on_main || h->stream_exposed) {
-            BM_HIP(hipEventRecord(h->ev_main, h->stream));
-            BM_HIP(hipStreamWaitEvent(rs, h->ev_main, 0));
-            h->engine_on_main = false;
-        }
-        BM_HIP(hipStreamWaitEvent(rs, h->ev_embs_free[h->pipe_slot], 0));
-    }
-    BM_HIP(hipMemsetAsync(h->d_crop_count, 0, 4, rs));
-    hipLaunchKernelGGL(build_crop_list_kernel, dim3(h->S), dim3(256), 0, rs, d_dets, d_ndets, h->nd, reid_thresh,
-                       h->d_crop_count, h->d_crop_stream, h->d_crop_boxes, h->d_crop_row, 0, inclusive);
-    if (h->reid->counted_ok()) {
-        h->reid->run_counted(d_frames, h->d_crop_stream, h->d_crop_boxes, 4, h->d_crop_count, h->S * h->nd, image_cols, image_rows,
-                             embs, h->d_crop_row, rs);
-    } else if (h->crop_bound >= 0) {
-        // launches sized by the caller's bound: no read-back, no stream synchronisation inside the step (the host keeps queueing)
-        const int n = h->crop_bound < h->S * h->nd ? h->crop_bound : h->S * h->nd;
-        int* nd_step = h->d_ndets_step[pipe ? h->pipe_slot : 0];        // (alternates with the embedding table: read by this call's step)
-        // (a bound of 0 -- "no crops in this step" -- is checked like any other: one workgroup compares the count with it)
-        hipLaunchKernelGGL(pad_crop_list_kernel, dim3(n > 0 ? (n + 255) / 256 : 1), dim3(256), 0, rs, (const int*)h->d_crop_count, n,
-                           h->d_crop_stream, h->d_crop_boxes, h->d_crop_row, h->d_crop_count + 1, d_ndets, nd_step, h->S);
+    if (core_reid_pass(h, rs, 0, h->S, d_dets, d_ndets, d_frames, image_rows, image_cols, reid_thresh, inclusive, embs, h->crop_bound, nd_step,
+                       &h->bounded_step_pending))
         h->step_ndets = nd_step;
-        h->bounded_step_pending = true;
-        if (n > 0) h->reid->run(d_frames, h->d_crop_stream, h->d_crop_boxes, 4, n, image_cols, image_rows, embs, h->d_crop_row, rs);
-    } else {
-        int n_crops = 0;
-        BM_HIP(hipMemcpyAsync(&n_crops, h->d_crop_count, 4, hipMemcpyDeviceToHost, rs));
-        BM_HIP(hipStreamSynchronize(rs));
-        h->reid->run(d_frames, h->d_crop_stream, h->d_crop_boxes, 4, n_crops, image_cols, image_rows, embs, h->d_crop_row, rs);
-    }
-    if (pipe) {
-        BM_HIP(hipEventRecord(h->ev_reid_done[h->pipe_slot], rs));
-        BM_HIP(hipStreamWaitEvent(h->stream, h->ev_reid_done[h->pipe_slot], 0));
-    }
+    core_pipe_reid_done(h);
     return embs;
-}
-// pipeline stage 2 enqueued (the frame step that reads this frame's embedding table is on `stream`): the table is free for the
-// ReID pass after next once that step has run
-void io_pipe_step_enqueued(StreamIo* h) {
-    if (!(h->pipe && h->reid_stream)) return;
-    BM_HIP(hipEventRecord(h->ev_embs_free[h->pipe_slot], h->stream));
-    h->pipe_slot ^= 1;
 }
 
 void io_set_crop_bound(StreamIo* h, int max_total_crops) {
@@ -1538,11 +1457,7 @@ void io_read_back(StreamIo* h, int n, const int* d_status, const char* tracker, 
         if (rows > out_capacity_rows) throw std::runtime_error("boxmot_hip: output buffer is too small for the current frame.");
         const size_t OC = h->out_cols;
         if (rows) BM_HIP(hipMemcpy(h->h_out.data(), h->d_out + (size_t)(s0 + k) * h->cap * OC, (size_t)rows * OC * 4, hipMemcpyDeviceToHost));
-        for (int r = 0; r < rows; ++r) {
-            float* dst = out[k] + (size_t)r * 9;
-            for (size_t q = 0; q < OC; ++q) dst[q] = h->h_out[(size_t)r * OC + q];
-            if (OC < 9) dst[8] = 0.0f;
-        }
+        copy_rows9(h->h_out.data(), rows, (int)OC, out[k]);
         out_rows[k] = rows;
     }
     if (!status_msg.empty()) throw std::runtime_error(status_msg);      // rows of this frame are in `out` all the same
@@ -1647,14 +1562,15 @@ void docs_grow(BoxMOTHipDeepOcSort* h, int new_cap, int new_nd) {
     std::vector<std::pair<void*, size_t>> rec;
     RecAlloc ra{&h->owned, &rec};
     bm::docs_allocate(na, bm::DocsSizes{h->S, new_cap, new_nd, h->dim, h->is_obb ? 1 : 0}, ra);
-    io_migrate(h, rec, na.sc.keep);
+    core_migrate(h, rec, na.sc.keep);
     h->args = na;
     const bool more_dets = new_nd != h->nd;
     h->cap = new_cap; h->nd = new_nd;
-    io_alloc_sized(h);
+    core_alloc_sized(h, h->cap, h->cap);        // result rows: [S][cap] on the device, one stream's at a time on the host
     if (new_reid) h->reid = std::move(new_reid);
     docs_set_lds(h, lds);
     if (h->args.dbg_cost) docs_make_dbg(h);
+    ++h->n_grows;
 }
 
 // Stage the inputs of the first n streams (ReID on every detection above det_thresh when embeddings are not supplied,
@@ -1740,17 +1656,18 @@ void ss_grow(BoxMOTHipStrongSort* h, int new_cap, int new_nd) {
     std::vector<std::pair<void*, size_t>> rec;
     RecAlloc ra{&h->owned, &rec};
     bm::ss_allocate(na, bm::SsSizes{h->S, new_cap, new_nd, h->dim, h->cfg.nn_budget}, ra);
-    io_migrate(h, rec, na.sc.app);
+    core_migrate(h, rec, na.sc.app);
     h->args = na;
     const bool more_dets = new_nd != h->nd;
     h->cap = new_cap; h->nd = new_nd;
-    io_alloc_sized(h);
-    if (more_dets && h->reid) io_make_reid(h);
+    core_alloc_sized(h, h->cap, h->cap);        // result rows: [S][cap] on the device, one stream's at a time on the host
+    if (more_dets && h->reid) h->reid = io_new_reid(h, h->nd);
     BM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(strongsort_step_kernel<STEP_THREADS>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     BM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(strongsort_step_kernel<SS_STEP_THREADS_BIG>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     if (h->args.dbg_cost) ss_make_dbg(h);
+    ++h->n_grows;
 }
 
 #ifdef BM_SS_PROF
@@ -1791,6 +1708,105 @@ void ss_host_update(BoxMOTHipStrongSort* h, int n, const StreamIn* in, int det_c
     a.out = h->d_out; a.out_n = h->d_out_n; a.stream_base = 0;
     ss_launch(h, a, n);
     io_read_back(h, n, h->args.st.status, "StrongSORT", out, out_capacity_rows, out_rows, 0, h->args.st.n_tracks);
+}
+
+// ---------------------------------------------------------------------------
+// Entry points that are the same for every tracker handle: `name` is the tracker as the messages spell it
+// ---------------------------------------------------------------------------
+void need_handle(const void* h, const char* name, const char* what) {
+    if (!h) throw std::runtime_error(std::string("boxmot_hip ") + name + " handle is " + what);
+}
+
+template <class H, class Zero>
+int ep_reset(H* h, const char* name, Zero zero_state) {
+    return guard_on(h, [&]() {
+        need_handle(h, name, "null.");
+        zero_state(h);
+        h->h_used.assign(h->S, 0);
+    });
+}
+
+template <class H, class Grow>
+int ep_reserve(H* h, const char* name, int max_tracks, int max_dets, Grow grow) {
+    return guard_on(h, [&]() {
+        need_handle(h, name, "null.");
+        const int cap = max_tracks > h->cap ? (max_tracks + 63) / 64 * 64 : h->cap;
+        const int nd = max_dets > h->nd ? (max_dets + 63) / 64 * 64 : h->nd;
+        if (cap != h->cap || nd != h->nd) grow(h, cap, nd);
+    });
+}
+
+template <class H>
+int ep_capacity(H* h, const char* name, int* max_tracks, int* max_dets, int* n_grows) {
+    return guard_on(h, [&]() {
+        need_handle(h, name, "null.");
+        if (max_tracks) *max_tracks = h->cap;
+        if (max_dets) *max_dets = h->nd;
+        if (n_grows) *n_grows = h->n_grows;
+    });
+}
+
+template <class H>
+int ep_set_warp(H* h, const char* name, int stream, const double* warp_2x3) {
+    return guard_on(h, [&]() {
+        need_handle(h, name, "null.");
+        core_set_warp(h, stream, warp_2x3);
+    });
+}
+
+template <class H>
+int ep_reid_kernel_ms(H* h, double* out_ms, int* out_launches) {
+    return guard_on(h, [&]() {
+        if (!h || !out_ms || !out_launches) throw std::runtime_error("boxmot_hip: null argument");
+        *out_ms = 0; *out_launches = 0;
+        if (h->reid) h->reid->drain_kernel_timing(*out_ms, *out_launches);
+    });
+}
+
+void* ep_stream(HandleCore* h) {
+    if (!h) return nullptr;
+    h->stream_exposed = true;
+    return (void*)h->stream;
+}
+
+// ---- DeepOCSORT / StrongSORT ----
+template <class H>
+int io_ep_set_reid_mode(H* h, int mode) {
+    return guard_on(h, [&]() {
+        if (!h || !h->reid) throw std::runtime_error("boxmot_hip: no ReID weights are loaded in this handle");
+        h->reid->set_mode(mode);
+        h->reid_mode = mode;
+    });
+}
+
+template <class H>
+int io_ep_synchronize(H* h, const char* name) {
+    return guard_on(h, [&]() {
+        need_handle(h, name, "not initialized.");
+        BM_HIP(hipStreamSynchronize(h->stream));
+        io_check_crop_bound(h);
+    });
+}
+
+template <class H>
+int io_ep_set_crop_bound(H* h, const char* name, int max_total_crops) {
+    return guard_on(h, [&]() {
+        need_handle(h, name, "not initialized.");
+        io_set_crop_bound(h, max_total_crops);
+    });
+}
+
+template <class H, class MakeDbg>
+int io_ep_debug_costs_enable(H* h, int on, MakeDbg make_dbg) {
+    return guard_on(h, [&]() {
+        if (!h) throw std::runtime_error("boxmot_hip: null argument");
+        BM_HIP(hipStreamSynchronize(h->stream));
+        if (on) make_dbg(h);
+        else if (h->args.dbg_cost) {
+            release(h->owned, h->args.dbg_cost); release(h->owned, h->args.dbg_shape);
+            h->args.dbg_cost = nullptr; h->args.dbg_shape = nullptr;
+        }
+    });
 }
 
 }  // namespace
@@ -1846,30 +1862,14 @@ BoxMOTHipBotSort* boxmot_hip_botsort_create(const BoxMOTHipBotSortConfig* config
 
 void boxmot_hip_botsort_destroy(BoxMOTHipBotSort* handle) { destroy_on(handle); }
 
-int boxmot_hip_botsort_reset(BoxMOTHipBotSort* handle) {
-    return guard_on(handle, [&]() {
-        if (!handle) throw std::runtime_error("boxmot_hip BoT-SORT handle is null.");
-        zero_state(handle);
-        handle->h_used.assign(handle->S, 0);
-    });
-}
+int boxmot_hip_botsort_reset(BoxMOTHipBotSort* handle) { return ep_reset(handle, "BoT-SORT", zero_state); }
 
 int boxmot_hip_botsort_reserve(BoxMOTHipBotSort* handle, int max_tracks, int max_dets) {
-    return guard_on(handle, [&]() {
-        if (!handle) throw std::runtime_error("boxmot_hip BoT-SORT handle is null.");
-        const int cap = max_tracks > handle->cap ? (max_tracks + 63) / 64 * 64 : handle->cap;
-        const int nd = max_dets > handle->nd ? (max_dets + 63) / 64 * 64 : handle->nd;
-        if (cap != handle->cap || nd != handle->nd) grow_tables(handle, cap, nd);
-    });
+    return ep_reserve(handle, "BoT-SORT", max_tracks, max_dets, grow_tables);
 }
 
 int boxmot_hip_botsort_capacity(BoxMOTHipBotSort* handle, int* max_tracks, int* max_dets, int* n_grows) {
-    return guard_on(handle, [&]() {
-        if (!handle) throw std::runtime_error("boxmot_hip BoT-SORT handle is null.");
-        if (max_tracks) *max_tracks = handle->cap;
-        if (max_dets) *max_dets = handle->nd;
-        if (n_grows) *n_grows = handle->n_grows;
-    });
+    return ep_capacity(handle, "BoT-SORT", max_tracks, max_dets, n_grows);
 }
 
 int boxmot_hip_botsort_update(BoxMOTHipBotSort* handle, const float* dets, int det_rows, int det_cols,
@@ -1910,7 +1910,7 @@ int boxmot_hip_botsort_update_batch(BoxMOTHipBotSort* handle, int n_streams, con
         std::vector<StreamIn> in(n_streams);
         for (int s = 0; s < n_streams; ++s)
             in[s] = StreamIn{dets[s], det_rows[s], (embs && emb_cols > 0) ? embs[s] : nullptr, images ? images[s] : nullptr};
-        host_update(handle, 0, n_streams, in.data(), handle->det_cols(), emb_cols, image_rows, image_cols, image_channels, nullptr, nullptr,
+        host_update(handle, 0, n_streams, in.data(), handle->det_cols, emb_cols, image_rows, image_cols, image_channels, nullptr, nullptr,
                     out_tracks, out_capacity_rows, out_rows);
     });
 }
@@ -1926,39 +1926,18 @@ int boxmot_hip_botsort_update_batch_frames(BoxMOTHipBotSort* handle, int n_strea
         if (!d_frames || (handle->fs_rows.empty() && (image_rows < 1 || image_cols < 1))) throw std::runtime_error("boxmot_hip: update_batch_frames needs device frames");
         std::vector<StreamIn> in(n_streams);
         for (int s = 0; s < n_streams; ++s) in[s] = StreamIn{dets[s], det_rows[s], (embs && emb_cols > 0) ? embs[s] : nullptr, nullptr};
-        host_update(handle, 0, n_streams, in.data(), handle->det_cols(), emb_cols, image_rows, image_cols, 3, nullptr, nullptr, out_tracks,
+        host_update(handle, 0, n_streams, in.data(), handle->det_cols, emb_cols, image_rows, image_cols, 3, nullptr, nullptr, out_tracks,
                     out_capacity_rows, out_rows, d_frames);
     });
 }
 
 int boxmot_hip_botsort_set_frame_sizes(BoxMOTHipBotSort* handle, const int* image_rows, const int* image_cols, int n_streams) {
     return guard_on(handle, [&]() {
-        if (!handle || !image_rows || !image_cols) throw std::runtime_error("boxmot_hip: null argument");
-        BoxMOTHipBotSort* h = handle;
-        if (n_streams != h->S) throw std::runtime_error("boxmot_hip: set_frame_sizes needs one (rows, cols) per stream of the handle (" + std::to_string(h->S) + ")");
-        for (int s = 0; s < h->S; ++s) {
-            if (image_rows[s] < 1 || image_cols[s] < 1) throw std::runtime_error("boxmot_hip: stream " + std::to_string(s) + ": frame dimensions must be positive");
-            // a stream's size is fixed by its first frame (or an earlier declaration)
-            const bool seen = h->frame_bufs[s] != nullptr || !h->fs_rows.empty();
-            const int r0 = h->fs_rows.empty() ? h->frame_rows : h->fs_rows[s], c0 = h->fs_cols.empty() ? h->frame_cols : h->fs_cols[s];
-            if (seen && (r0 != image_rows[s] || c0 != image_cols[s]))
-                throw std::runtime_error("boxmot_hip: stream " + std::to_string(s) + ": frame size changed (" + std::to_string(r0) + " x " + std::to_string(c0) +
-                                         " -> " + std::to_string(image_rows[s]) + " x " + std::to_string(image_cols[s]) + ")");
-        }
-        if ((h->sof || h->ecc) && h->fs_rows.empty())
+        if (!handle) throw std::runtime_error("boxmot_hip: null argument");
+        core_check_frame_sizes(handle, image_rows, image_cols, n_streams);
+        if ((handle->sof || handle->ecc) && handle->fs_rows.empty())
             throw std::runtime_error("boxmot_hip: set_frame_sizes comes before the first update of a handle that estimates camera motion itself");
-        BM_HIP(hipStreamSynchronize(h->stream));
-        if (h->reid_stream) BM_HIP(hipStreamSynchronize(h->reid_stream));
-        h->fs_rows.assign(image_rows, image_rows + h->S);
-        h->fs_cols.assign(image_cols, image_cols + h->S);
-        h->fs_mixed = false;
-        std::vector<int> dims((size_t)h->S * 2);
-        for (int s = 0; s < h->S; ++s) {
-            dims[2 * s] = image_cols[s]; dims[2 * s + 1] = image_rows[s];
-            if (image_rows[s] != image_rows[0] || image_cols[s] != image_cols[0]) h->fs_mixed = true;
-        }
-        if (!h->d_fs_dims) h->d_fs_dims = dev_alloc<int>((size_t)h->S * 2, h->owned);
-        BM_HIP(hipMemcpy(h->d_fs_dims, dims.data(), dims.size() * sizeof(int), hipMemcpyHostToDevice));
+        core_commit_frame_sizes(handle, image_rows, image_cols);
     });
 }
 
@@ -1969,29 +1948,16 @@ int boxmot_hip_botsort_step_device(BoxMOTHipBotSort* handle, const float* d_dets
         if (!handle) throw std::runtime_error("boxmot_hip BoT-SORT handle is not initialized.");
         if (!d_dets || !d_det_rows || !d_out || !d_out_rows) throw std::runtime_error("boxmot_hip: null device pointers");
         const float* embs = d_embs;
-        bool piped = false;
+        bool reid_here = false;
         if (handle->cfg.with_reid && d_embs == nullptr) {
             if (handle->is_obb) throw std::runtime_error("boxmot_hip: an oriented-box handle with with_reid = 1 needs d_embs");
             if (!d_frames) throw std::runtime_error("boxmot_hip: with_reid needs d_embs or d_frames");
             // pipeline stage 1: this frame's ReID on `reid_stream`, into the table the step before last has finished reading
-            const bool pipe = handle->pipe && handle->reid_stream;
-            float* tab = (pipe && handle->pipe_slot) ? handle->d_embs_alt : handle->d_embs;
-            if (pipe) {
-                hipStream_t rs = handle->reid_stream;
-                if (handle->engine_on_main || handle->stream_exposed) {       // (as io_device_reid: engine used on `stream`, or the caller holds `stream`)
-                    BM_HIP(hipEventRecord(handle->ev_main, handle->stream));
-                    BM_HIP(hipStreamWaitEvent(rs, handle->ev_main, 0));
-                    handle->engine_on_main = false;
-                }
-                BM_HIP(hipStreamWaitEvent(rs, handle->ev_embs_free[handle->pipe_slot], 0));
-                run_reid(handle, 0, handle->S, d_dets, d_det_rows, d_frames, image_rows, image_cols, tab, rs);
-                BM_HIP(hipEventRecord(handle->ev_reid_done[handle->pipe_slot], rs));
-                BM_HIP(hipStreamWaitEvent(handle->stream, handle->ev_reid_done[handle->pipe_slot], 0));
-                piped = true;
-            } else {
-                run_reid(handle, 0, handle->S, d_dets, d_det_rows, d_frames, image_rows, image_cols, tab);
-            }
-            embs = tab;
+            hipStream_t rs = core_pipe_begin_reid(handle);
+            float* tab = core_pipe_table(handle);
+            run_reid(handle, rs, 0, handle->S, d_dets, d_det_rows, d_frames, image_rows, image_cols, tab);
+            core_pipe_reid_done(handle);
+            embs = tab; reid_here = true;
         }
         // cmc_method = "sof" / "ecc": the estimator runs inside the step here too, on the device-resident frames, for every stream
         // that was not given a warp with set_warp (the estimate comes back to the host: one synchronisation per step; callers that
@@ -2027,25 +1993,13 @@ int boxmot_hip_botsort_step_device(BoxMOTHipBotSort* handle, const float* d_dets
         }
         launch_step(handle, 0, handle->S, d_dets, d_det_rows, handle->cfg.with_reid ? embs : nullptr, nullptr, nullptr,
                     d_out, d_out_rows, any_warp);
-        if (piped) {        // pipeline stage 2 enqueued: the table is free for the ReID pass after next once this step has run
-            BM_HIP(hipEventRecord(handle->ev_embs_free[handle->pipe_slot], handle->stream));
-            handle->pipe_slot ^= 1;
-        }
+        if (reid_here) core_pipe_step_enqueued(handle);
         for (int s = 0; s < handle->S; ++s) { handle->h_warp_flag[s] = 0; handle->h_used[s] = -1; }      // slot counts: unknown to the host now
     });
 }
 
 int boxmot_hip_botsort_set_warp(BoxMOTHipBotSort* handle, int stream, const double* warp_2x3) {
-    return guard_on(handle, [&]() {
-        if (!handle) throw std::runtime_error("boxmot_hip BoT-SORT handle is null.");
-        if (stream < 0 || stream >= handle->S) throw std::runtime_error("boxmot_hip: stream index out of range");
-        if (warp_2x3 == nullptr) { handle->h_warp_flag[stream] = 0; return; }
-        for (int k = 0; k < 6; ++k) {
-            if (!std::isfinite(warp_2x3[k])) throw std::runtime_error("boxmot_hip: camera-motion warp has non-finite entries");
-            handle->h_warp[(size_t)stream * 6 + k] = warp_2x3[k];
-        }
-        handle->h_warp_flag[stream] = 1;
-    });
+    return ep_set_warp(handle, "BoT-SORT", stream, warp_2x3);
 }
 
 int boxmot_hip_botsort_synchronize(BoxMOTHipBotSort* handle) {
@@ -2073,13 +2027,7 @@ int boxmot_hip_botsort_timer_stop_ms(BoxMOTHipBotSort* handle, double* out_ms) {
     });
 }
 
-int boxmot_hip_botsort_reid_kernel_ms(BoxMOTHipBotSort* handle, double* out_ms, int* out_launches) {
-    return guard_on(handle, [&]() {
-        if (!handle || !out_ms || !out_launches) throw std::runtime_error("boxmot_hip: null argument");
-        *out_ms = 0; *out_launches = 0;
-        if (handle->reid) handle->reid->drain_kernel_timing(*out_ms, *out_launches);
-    });
-}
+int boxmot_hip_botsort_reid_kernel_ms(BoxMOTHipBotSort* handle, double* out_ms, int* out_launches) { return ep_reid_kernel_ms(handle, out_ms, out_launches); }
 
 int boxmot_hip_botsort_phase_clocks(BoxMOTHipBotSort* handle, long long* out16) {
     return guard_on(handle, [&]() {
@@ -2089,7 +2037,7 @@ int boxmot_hip_botsort_phase_clocks(BoxMOTHipBotSort* handle, long long* out16) 
     });
 }
 
-void* boxmot_hip_botsort_stream(BoxMOTHipBotSort* handle) { if (handle) handle->stream_exposed = true; return handle ? (void*)handle->stream : nullptr; }
+void* boxmot_hip_botsort_stream(BoxMOTHipBotSort* handle) { return ep_stream(handle); }
 
 int boxmot_hip_botsort_status(BoxMOTHipBotSort* handle, int* out_status, int capacity) {
     return guard_on(handle, [&]() {
@@ -2166,7 +2114,7 @@ int boxmot_hip_botsort_state_dump(BoxMOTHipBotSort* handle, int stream, int whic
         const auto id = pull_i(st.id), state = pull_i(st.state), act = pull_i(st.is_activated), fid = pull_i(st.frame_id),
                    sf = pull_i(st.start_frame), tl = pull_i(st.tracklet_len);
         const auto conf = pull_f(st.conf), cls = pull_f(st.cls), di = pull_f(st.det_ind);
-        const size_t KS = handle->kf_stride();        // 72 doubles per track (mean 8 + cov 64), 110 for oriented boxes (10 + 100)
+        const size_t KS = handle->is_obb ? bm::obb::KF_STRIDE : bm::KF_STRIDE;        // 72 doubles per track (mean 8 + cov 64), 110 for oriented boxes (10 + 100)
         std::vector<double> kfall(cap * KS);
         BM_HIP(hipMemcpy(kfall.data(), st.kf + s * cap * KS, kfall.size() * 8, hipMemcpyDeviceToHost));
         std::vector<float> sm;
@@ -2349,11 +2297,7 @@ int boxmot_hip_reid_compute_features(BoxMOTHipReID* handle, const uint8_t* image
 }
 
 // ---- boxes of many images, of any sizes, in one device pass ----
-// the per-image frame sizes are valid for one batch call only
-struct DimsScope {
-    BoxMOTHipReID* h;
-    ~DimsScope() { if (h && h->engine) { h->engine->set_frame_dims(nullptr); h->engine->set_obb_geometry(nullptr); } }
-};
+// (the per-image frame sizes, like the oriented-box geometry, are valid for one batch call only: FrameDimsScope, ObbScope)
 
 // Validate, upload the images, bring the pointer and {W, H} tables up to date.  Returns whether the images differ in size (the
 // engine then reads the table; with one size the scalar-form kernels run, as for a single image).
@@ -2429,7 +2373,8 @@ int boxmot_hip_reid_compute_features_batch(BoxMOTHipReID* handle, const uint8_t*
                                            const int* image_cols, int n_images, const float* boxes, const int* box_image, int n_boxes,
                                            int box_cols, float* out_features, int out_capacity_rows) {
     return guard_on(handle, [&]() {
-        DimsScope scope{handle};
+        ObbScope obb_scope{handle};
+        FrameDimsScope dims_scope{handle ? handle->engine.get() : nullptr};
         const bool mixed = reid_stage_images(handle, images, image_rows, image_cols, n_images, box_image, n_boxes, box_cols);
         if (out_capacity_rows < n_boxes) throw std::runtime_error("boxmot_hip: feature buffer too small");
         if (n_boxes > 0 && !out_features) throw std::runtime_error("boxmot_hip: null argument");
@@ -2450,7 +2395,8 @@ int boxmot_hip_reid_compute_features_batch(BoxMOTHipReID* handle, const uint8_t*
 int boxmot_hip_reid_preprocess_batch(BoxMOTHipReID* handle, const uint8_t* const* images, const int* image_rows, const int* image_cols,
                                      int n_images, const float* boxes, const int* box_image, int n_boxes, int box_cols, float* out_crops) {
     return guard_on(handle, [&]() {
-        DimsScope scope{handle};
+        ObbScope obb_scope{handle};
+        FrameDimsScope dims_scope{handle ? handle->engine.get() : nullptr};
         const bool mixed = reid_stage_images(handle, images, image_rows, image_cols, n_images, box_image, n_boxes, box_cols);
         if (n_boxes > handle->engine->max_crops()) throw std::runtime_error("boxmot_hip: more boxes than max_crops");
         if (n_boxes == 0) { BM_HIP(hipStreamSynchronize(handle->stream)); return; }
@@ -2782,37 +2728,21 @@ BoxMOTHipDeepOcSort* boxmot_hip_deepocsort_create(const BoxMOTHipDeepOcSortConfi
 
 void boxmot_hip_deepocsort_destroy(BoxMOTHipDeepOcSort* handle) { destroy_on(handle); }
 
-int boxmot_hip_deepocsort_reset(BoxMOTHipDeepOcSort* handle) {
-    return guard_on(handle, [&]() {
-        if (!handle) throw std::runtime_error("boxmot_hip DeepOCSORT handle is null.");
-        docs_zero_state(handle);
-        handle->h_used.assign(handle->S, 0);
-    });
-}
+int boxmot_hip_deepocsort_reset(BoxMOTHipDeepOcSort* handle) { return ep_reset(handle, "DeepOCSORT", docs_zero_state); }
 
 int boxmot_hip_deepocsort_reserve(BoxMOTHipDeepOcSort* handle, int max_tracks, int max_dets) {
-    return guard_on(handle, [&]() {
-        if (!handle) throw std::runtime_error("boxmot_hip DeepOCSORT handle is null.");
-        const int cap = max_tracks > handle->cap ? (max_tracks + 63) / 64 * 64 : handle->cap;
-        const int nd = max_dets > handle->nd ? (max_dets + 63) / 64 * 64 : handle->nd;
-        if (cap != handle->cap || nd != handle->nd) { docs_grow(handle, cap, nd); ++handle->n_grows; }
-    });
+    return ep_reserve(handle, "DeepOCSORT", max_tracks, max_dets, docs_grow);
 }
 
 int boxmot_hip_deepocsort_capacity(BoxMOTHipDeepOcSort* handle, int* max_tracks, int* max_dets, int* n_grows) {
-    return guard_on(handle, [&]() {
-        if (!handle) throw std::runtime_error("boxmot_hip DeepOCSORT handle is null.");
-        if (max_tracks) *max_tracks = handle->cap;
-        if (max_dets) *max_dets = handle->nd;
-        if (n_grows) *n_grows = handle->n_grows;
-    });
+    return ep_capacity(handle, "DeepOCSORT", max_tracks, max_dets, n_grows);
 }
 
 int boxmot_hip_deepocsort_set_warp(BoxMOTHipDeepOcSort* handle, int stream, const double* warp_2x3) {
     return guard_on(handle, [&]() {
         if (!handle) throw std::runtime_error("boxmot_hip DeepOCSORT handle is null.");
         if (handle->is_obb && warp_2x3) throw std::runtime_error("boxmot_hip: camera-motion warps are not applied to oriented detections");
-        io_set_warp(handle, stream, warp_2x3);
+        core_set_warp(handle, stream, warp_2x3);
     });
 }
 
@@ -2905,7 +2835,7 @@ int boxmot_hip_deepocsort_step_device_frames(BoxMOTHipDeepOcSort* handle, const 
         a.out = d_out; a.out_n = d_out_rows; a.stream_base = 0;
         docs_launch(handle, handle->S, a);
         BM_HIP(hipGetLastError());
-        if (embs) io_pipe_step_enqueued(handle);
+        if (embs) core_pipe_step_enqueued(handle);
         io_clear_warps(handle);
     });
 }
@@ -2920,42 +2850,22 @@ int boxmot_hip_deepocsort_set_frame_sizes(BoxMOTHipDeepOcSort* handle, const int
                 if (image_rows[s] != image_rows[0] || image_cols[s] != image_cols[0])
                     throw std::runtime_error("boxmot_hip: asso_func centroid normalises by one frame diagonal per handle: streams of different "
                                              "frame sizes (stream " + std::to_string(s) + " differs from stream 0) need another asso_func or one handle per size");
-        io_set_frame_sizes(handle, image_rows, image_cols, n_streams);
+        core_check_frame_sizes(handle, image_rows, image_cols, n_streams);
+        core_commit_frame_sizes(handle, image_rows, image_cols);
         docs_need_frame_size(handle, image_rows[0], image_cols[0]);       // (one size: centroid takes it, if the config gave none)
     });
 }
 
-int boxmot_hip_deepocsort_set_reid_mode(BoxMOTHipDeepOcSort* handle, int mode) {
-    return guard_on(handle, [&]() {
-        if (!handle || !handle->reid) throw std::runtime_error("boxmot_hip: no ReID weights are loaded in this handle");
-        handle->reid->set_mode(mode);
-        handle->reid_mode = mode;
-    });
-}
+int boxmot_hip_deepocsort_set_reid_mode(BoxMOTHipDeepOcSort* handle, int mode) { return io_ep_set_reid_mode(handle, mode); }
 
-int boxmot_hip_deepocsort_reid_kernel_ms(BoxMOTHipDeepOcSort* handle, double* out_ms, int* out_launches) {
-    return guard_on(handle, [&]() {
-        if (!handle || !out_ms || !out_launches) throw std::runtime_error("boxmot_hip: null argument");
-        *out_ms = 0; *out_launches = 0;
-        if (handle->reid) handle->reid->drain_kernel_timing(*out_ms, *out_launches);
-    });
-}
+int boxmot_hip_deepocsort_reid_kernel_ms(BoxMOTHipDeepOcSort* handle, double* out_ms, int* out_launches) { return ep_reid_kernel_ms(handle, out_ms, out_launches); }
 
-void* boxmot_hip_deepocsort_stream(BoxMOTHipDeepOcSort* handle) { if (handle) handle->stream_exposed = true; return handle ? (void*)handle->stream : nullptr; }
+void* boxmot_hip_deepocsort_stream(BoxMOTHipDeepOcSort* handle) { return ep_stream(handle); }
 
-int boxmot_hip_deepocsort_synchronize(BoxMOTHipDeepOcSort* handle) {
-    return guard_on(handle, [&]() {
-        if (!handle) throw std::runtime_error("boxmot_hip DeepOCSORT handle is not initialized.");
-        BM_HIP(hipStreamSynchronize(handle->stream));
-        io_check_crop_bound(handle);
-    });
-}
+int boxmot_hip_deepocsort_synchronize(BoxMOTHipDeepOcSort* handle) { return io_ep_synchronize(handle, "DeepOCSORT"); }
 
 int boxmot_hip_deepocsort_set_crop_bound(BoxMOTHipDeepOcSort* handle, int max_total_crops) {
-    return guard_on(handle, [&]() {
-        if (!handle) throw std::runtime_error("boxmot_hip DeepOCSORT handle is not initialized.");
-        io_set_crop_bound(handle, max_total_crops);
-    });
+    return io_ep_set_crop_bound(handle, "DeepOCSORT", max_total_crops);
 }
 
 int boxmot_hip_deepocsort_state_dump(BoxMOTHipDeepOcSort* handle, int stream, int* ints5, double* kf72, double* emb,
@@ -3016,37 +2926,18 @@ BoxMOTHipStrongSort* boxmot_hip_strongsort_create(const BoxMOTHipStrongSortConfi
 
 void boxmot_hip_strongsort_destroy(BoxMOTHipStrongSort* handle) { destroy_on(handle); }
 
-int boxmot_hip_strongsort_reset(BoxMOTHipStrongSort* handle) {
-    return guard_on(handle, [&]() {
-        if (!handle) throw std::runtime_error("boxmot_hip StrongSORT handle is null.");
-        ss_zero_state(handle);
-        handle->h_used.assign(handle->S, 0);
-    });
-}
+int boxmot_hip_strongsort_reset(BoxMOTHipStrongSort* handle) { return ep_reset(handle, "StrongSORT", ss_zero_state); }
 
 int boxmot_hip_strongsort_reserve(BoxMOTHipStrongSort* handle, int max_tracks, int max_dets) {
-    return guard_on(handle, [&]() {
-        if (!handle) throw std::runtime_error("boxmot_hip StrongSORT handle is null.");
-        const int cap = max_tracks > handle->cap ? (max_tracks + 63) / 64 * 64 : handle->cap;
-        const int nd = max_dets > handle->nd ? (max_dets + 63) / 64 * 64 : handle->nd;
-        if (cap != handle->cap || nd != handle->nd) { ss_grow(handle, cap, nd); ++handle->n_grows; }
-    });
+    return ep_reserve(handle, "StrongSORT", max_tracks, max_dets, ss_grow);
 }
 
 int boxmot_hip_strongsort_capacity(BoxMOTHipStrongSort* handle, int* max_tracks, int* max_dets, int* n_grows) {
-    return guard_on(handle, [&]() {
-        if (!handle) throw std::runtime_error("boxmot_hip StrongSORT handle is null.");
-        if (max_tracks) *max_tracks = handle->cap;
-        if (max_dets) *max_dets = handle->nd;
-        if (n_grows) *n_grows = handle->n_grows;
-    });
+    return ep_capacity(handle, "StrongSORT", max_tracks, max_dets, n_grows);
 }
 
 int boxmot_hip_strongsort_set_warp(BoxMOTHipStrongSort* handle, int stream, const double* warp_2x3) {
-    return guard_on(handle, [&]() {
-        if (!handle) throw std::runtime_error("boxmot_hip StrongSORT handle is null.");
-        io_set_warp(handle, stream, warp_2x3);
-    });
+    return ep_set_warp(handle, "StrongSORT", stream, warp_2x3);
 }
 
 int boxmot_hip_strongsort_update_batch(BoxMOTHipStrongSort* handle, int n_streams, const float* const* dets,
@@ -3110,7 +3001,7 @@ int boxmot_hip_strongsort_step_device_frames(BoxMOTHipStrongSort* handle, const 
         a.out = d_out; a.out_n = d_out_rows; a.stream_base = 0;
         ss_launch(handle, a, handle->S);
         BM_HIP(hipGetLastError());
-        io_pipe_step_enqueued(handle);
+        core_pipe_step_enqueued(handle);
         io_clear_warps(handle);
     });
 }
@@ -3118,25 +3009,14 @@ int boxmot_hip_strongsort_step_device_frames(BoxMOTHipStrongSort* handle, const 
 int boxmot_hip_strongsort_set_frame_sizes(BoxMOTHipStrongSort* handle, const int* image_rows, const int* image_cols, int n_streams) {
     return guard_on(handle, [&]() {
         if (!handle) throw std::runtime_error("boxmot_hip StrongSORT handle is not initialized.");
-        io_set_frame_sizes(handle, image_rows, image_cols, n_streams);
+        core_check_frame_sizes(handle, image_rows, image_cols, n_streams);
+        core_commit_frame_sizes(handle, image_rows, image_cols);
     });
 }
 
-int boxmot_hip_strongsort_set_reid_mode(BoxMOTHipStrongSort* handle, int mode) {
-    return guard_on(handle, [&]() {
-        if (!handle || !handle->reid) throw std::runtime_error("boxmot_hip: no ReID weights are loaded in this handle");
-        handle->reid->set_mode(mode);
-        handle->reid_mode = mode;
-    });
-}
+int boxmot_hip_strongsort_set_reid_mode(BoxMOTHipStrongSort* handle, int mode) { return io_ep_set_reid_mode(handle, mode); }
 
-int boxmot_hip_strongsort_reid_kernel_ms(BoxMOTHipStrongSort* handle, double* out_ms, int* out_launches) {
-    return guard_on(handle, [&]() {
-        if (!handle || !out_ms || !out_launches) throw std::runtime_error("boxmot_hip: null argument");
-        *out_ms = 0; *out_launches = 0;
-        if (handle->reid) handle->reid->drain_kernel_timing(*out_ms, *out_launches);
-    });
-}
+int boxmot_hip_strongsort_reid_kernel_ms(BoxMOTHipStrongSort* handle, double* out_ms, int* out_launches) { return ep_reid_kernel_ms(handle, out_ms, out_launches); }
 
 int boxmot_hip_strongsort_track_count(BoxMOTHipStrongSort* handle, int stream, int* out_tracks) {
     return guard_on(handle, [&]() {
@@ -3148,34 +3028,15 @@ int boxmot_hip_strongsort_track_count(BoxMOTHipStrongSort* handle, int stream, i
     });
 }
 
-void* boxmot_hip_strongsort_stream(BoxMOTHipStrongSort* handle) { if (handle) handle->stream_exposed = true; return handle ? (void*)handle->stream : nullptr; }
+void* boxmot_hip_strongsort_stream(BoxMOTHipStrongSort* handle) { return ep_stream(handle); }
 
-int boxmot_hip_strongsort_synchronize(BoxMOTHipStrongSort* handle) {
-    return guard_on(handle, [&]() {
-        if (!handle) throw std::runtime_error("boxmot_hip StrongSORT handle is not initialized.");
-        BM_HIP(hipStreamSynchronize(handle->stream));
-        io_check_crop_bound(handle);
-    });
-}
+int boxmot_hip_strongsort_synchronize(BoxMOTHipStrongSort* handle) { return io_ep_synchronize(handle, "StrongSORT"); }
 
 int boxmot_hip_strongsort_set_crop_bound(BoxMOTHipStrongSort* handle, int max_total_crops) {
-    return guard_on(handle, [&]() {
-        if (!handle) throw std::runtime_error("boxmot_hip StrongSORT handle is not initialized.");
-        io_set_crop_bound(handle, max_total_crops);
-    });
+    return io_ep_set_crop_bound(handle, "StrongSORT", max_total_crops);
 }
 
-int boxmot_hip_deepocsort_debug_costs_enable(BoxMOTHipDeepOcSort* handle, int on) {
-    return guard_on(handle, [&]() {
-        if (!handle) throw std::runtime_error("boxmot_hip: null argument");
-        BM_HIP(hipStreamSynchronize(handle->stream));
-        if (on) docs_make_dbg(handle);
-        else if (handle->args.dbg_cost) {
-            release(handle->owned, handle->args.dbg_cost); release(handle->owned, handle->args.dbg_shape);
-            handle->args.dbg_cost = nullptr; handle->args.dbg_shape = nullptr;
-        }
-    });
-}
+int boxmot_hip_deepocsort_debug_costs_enable(BoxMOTHipDeepOcSort* handle, int on) { return io_ep_debug_costs_enable(handle, on, docs_make_dbg); }
 
 int boxmot_hip_deepocsort_debug_costs(BoxMOTHipDeepOcSort* handle, int stream, int plane, double* out, long out_capacity,
                                       int* out_rows, int* out_cols, int* out_branch) {
@@ -3200,17 +3061,7 @@ int boxmot_hip_deepocsort_debug_costs(BoxMOTHipDeepOcSort* handle, int stream, i
     });
 }
 
-int boxmot_hip_strongsort_debug_costs_enable(BoxMOTHipStrongSort* handle, int on) {
-    return guard_on(handle, [&]() {
-        if (!handle) throw std::runtime_error("boxmot_hip: null argument");
-        BM_HIP(hipStreamSynchronize(handle->stream));
-        if (on) ss_make_dbg(handle);
-        else if (handle->args.dbg_cost) {
-            release(handle->owned, handle->args.dbg_cost); release(handle->owned, handle->args.dbg_shape);
-            handle->args.dbg_cost = nullptr; handle->args.dbg_shape = nullptr;
-        }
-    });
-}
+int boxmot_hip_strongsort_debug_costs_enable(BoxMOTHipStrongSort* handle, int on) { return io_ep_debug_costs_enable(handle, on, ss_make_dbg); }
 
 int boxmot_hip_strongsort_debug_costs(BoxMOTHipStrongSort* handle, int stream, int stage, int plane, double* out, long out_capacity,
                                       int* out_rows, int* out_cols) {
