@@ -219,6 +219,10 @@ SIGNATURES = {
     "boxmot_hip_ingest_wait": (_I, [_VP, _I, _VP]),
     "boxmot_hip_ingest_release": (_I, [_VP, _I, _VP]),
     "boxmot_hip_ingest_host_done": (_I, [_VP, _I]),
+    "boxmot_hip_ingest_create_nv12": (_VP, [_I, _I, _VP, _VP]),
+    "boxmot_hip_ingest_submit_device_nv12": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP]),
+    "boxmot_hip_ingest_format": (_I, [_VP]),
+    "boxmot_hip_ingest_download": (_I, [_VP, _I, _I, _VP]),
     "boxmot_hip_last_error": (ctypes.c_char_p, []),
     "boxmot_hip_device_count": (_I, []),
     "boxmot_hip_botsort_device": (_I, [_VP]),

@@ -22,6 +22,7 @@
 #include "reid_engine.hpp"
 #include "cmc_ecc.hpp"
 #include "cmc_sof.hpp"
+#include "ingest_nv12.hpp"
 
 namespace {
 
@@ -312,20 +313,34 @@ struct BoxMOTHipSof : DeviceBound {
 // one "uploaded" + one "consumed" event per slot.  The caller decodes frame t + 1 straight into slot (t + 1) % n_slots while the
 // kernels of frame t run; submit() queues the slot's H2D DMA on the copy stream, wait() makes the consuming stream wait for it,
 // release() lets the next upload into the slot wait for the consumer -- no host synchronisation anywhere.
+// An NV12 ring (format 1) keeps the host slots and a device staging twin in NV12 (1.5 bytes per pixel over PCIe) and converts into the
+// same BGR device frames with one k_nv12_to_bgr launch behind the DMA on the copy stream (csrc/ingest_nv12.hpp).
 struct BoxMOTHipIngest : DeviceBound {
     int n_slots = 0, n_streams = 0, rows = 0, cols = 0;
+    int format = 0;                                 // 0: the host slots hold BGR frames, 1: NV12 frames
     size_t frame_bytes = 0;
+    std::vector<int> srows, scols;                  // [n_streams]: image size of each stream
     std::vector<size_t> offs;                       // [n_streams + 1]: byte offset of each stream's frame inside a slot (one allocation, one DMA)
+    std::vector<size_t> nv_offs;                    // NV12 rings: the same for the NV12 frames of the host slot and its staging twin
     hipStream_t copy_stream = nullptr;
-    std::vector<uint8_t*> h_slot, d_slot;           // [n_slots]: n_streams contiguous frames each
+    std::vector<uint8_t*> h_slot, d_slot;           // [n_slots]: n_streams contiguous frames each (h_slot: in the ring's format; d_slot: BGR)
+    std::vector<uint8_t*> d_nv;                     // [n_slots] NV12 rings: device twin of h_slot
     std::vector<const uint8_t**> d_ptrs;            // [n_slots]: device table of n_streams frame pointers
+    std::vector<std::vector<bm::Nv12Desc>> nv_desc; // [n_slots] NV12 rings: staging twin -> BGR frames, and that table on the device
+    std::vector<bm::Nv12Desc*> d_desc;
+    std::vector<bm::Nv12Desc*> h_ext, d_ext;        // [n_slots] submit_device_nv12: pinned staging of the caller's surfaces and its device twin
+    std::vector<char> ext_used;
     std::vector<hipEvent_t> uploaded, consumed;
     std::vector<char> has_consumer;
     ~BoxMOTHipIngest() {
         if (copy_stream) (void)hipStreamSynchronize(copy_stream);
         for (auto p : h_slot) if (p) (void)hipHostFree(p);
         for (auto p : d_slot) if (p) (void)hipFree(p);
+        for (auto p : d_nv) if (p) (void)hipFree(p);
         for (auto p : d_ptrs) if (p) (void)hipFree(p);
+        for (auto p : d_desc) if (p) (void)hipFree(p);
+        for (auto p : h_ext) if (p) (void)hipHostFree(p);
+        for (auto p : d_ext) if (p) (void)hipFree(p);
         for (auto e : uploaded) (void)hipEventDestroy(e);
         for (auto e : consumed) (void)hipEventDestroy(e);
         if (copy_stream) (void)hipStreamDestroy(copy_stream);
@@ -2581,10 +2596,10 @@ int boxmot_hip_sof_debug_map(BoxMOTHipSof* handle, int stream, int which, void* 
 static void ingest_build(BoxMOTHipIngest* h) {
     const int n_slots = h->n_slots, n_streams = h->n_streams;
     BM_HIP(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-    const size_t slot_bytes = h->offs[n_streams];
+    const size_t slot_bytes = h->offs[n_streams], host_bytes = h->format ? h->nv_offs[n_streams] : slot_bytes;
     for (int k = 0; k < n_slots; ++k) {
         void *hp = nullptr, *dp = nullptr, *tp = nullptr;
-        BM_HIP(hipHostMalloc(&hp, slot_bytes, hipHostMallocDefault));
+        BM_HIP(hipHostMalloc(&hp, host_bytes, hipHostMallocDefault));
         h->h_slot.push_back(static_cast<uint8_t*>(hp));
         BM_HIP(hipMalloc(&dp, slot_bytes));
         h->d_slot.push_back(static_cast<uint8_t*>(dp));
@@ -2593,6 +2608,21 @@ static void ingest_build(BoxMOTHipIngest* h) {
         std::vector<const uint8_t*> table(n_streams);
         for (int s = 0; s < n_streams; ++s) table[s] = h->d_slot[k] + h->offs[s];
         BM_HIP(hipMemcpy(tp, table.data(), n_streams * sizeof(uint8_t*), hipMemcpyHostToDevice));
+        if (h->format) {                // NV12 staging twin (pitch = cols, UV directly after Y) and its conversion descriptors
+            void *np = nullptr, *qp = nullptr;
+            BM_HIP(hipMalloc(&np, host_bytes));
+            h->d_nv.push_back(static_cast<uint8_t*>(np));
+            std::vector<bm::Nv12Desc> desc(n_streams);
+            for (int s = 0; s < n_streams; ++s) {
+                const uint8_t* y = h->d_nv[k] + h->nv_offs[s];
+                desc[s] = bm::Nv12Desc{y, y + (size_t)h->srows[s] * h->scols[s], h->scols[s], h->scols[s], h->srows[s], h->scols[s],
+                                       h->d_slot[k] + h->offs[s]};
+            }
+            BM_HIP(hipMalloc(&qp, n_streams * sizeof(bm::Nv12Desc)));
+            h->d_desc.push_back(static_cast<bm::Nv12Desc*>(qp));
+            BM_HIP(hipMemcpy(qp, desc.data(), n_streams * sizeof(bm::Nv12Desc), hipMemcpyHostToDevice));
+            h->nv_desc.push_back(std::move(desc));
+        }
         hipEvent_t a, b;
         BM_HIP(hipEventCreateWithFlags(&a, hipEventDisableTiming));
         BM_HIP(hipEventCreateWithFlags(&b, hipEventDisableTiming));
@@ -2610,6 +2640,7 @@ BoxMOTHipIngest* boxmot_hip_ingest_create(int n_slots, int n_streams, int image_
         h = new BoxMOTHipIngest();
         h->n_slots = n_slots; h->n_streams = n_streams; h->rows = image_rows; h->cols = image_cols;
         h->frame_bytes = (size_t)image_rows * image_cols * 3;
+        h->srows.assign(n_streams, image_rows); h->scols.assign(n_streams, image_cols);
         h->offs.resize((size_t)n_streams + 1);
         for (int s = 0; s <= n_streams; ++s) h->offs[s] = (size_t)s * h->frame_bytes;
         ingest_build(h);
@@ -2632,6 +2663,7 @@ BoxMOTHipIngest* boxmot_hip_ingest_create_sized(int n_slots, int n_streams, cons
         h = new BoxMOTHipIngest();
         h->n_slots = n_slots; h->n_streams = n_streams; h->rows = image_rows[0]; h->cols = image_cols[0];
         h->frame_bytes = 0;             // (no single frame size)
+        h->srows.assign(image_rows, image_rows + n_streams); h->scols.assign(image_cols, image_cols + n_streams);
         h->offs.assign((size_t)n_streams + 1, 0);
         for (int s = 0; s < n_streams; ++s)
             h->offs[s + 1] = (h->offs[s] + (size_t)image_rows[s] * image_cols[s] * 3 + 255) / 256 * 256;
@@ -2640,6 +2672,41 @@ BoxMOTHipIngest* boxmot_hip_ingest_create_sized(int n_slots, int n_streams, cons
     if (!ok) { delete h; return nullptr; }
     return h;
 }
+
+// a ring whose host slots hold NV12 frames (tightly packed: pitch = cols, the UV plane directly after the Y plane; frames at 256-byte
+// aligned offsets): submit moves the NV12 bytes and converts them into the BGR device frames -- laid out as create_sized lays them
+// out -- on the copy stream.  Sizes are per stream (a uniform ring passes equal entries) and even.
+BoxMOTHipIngest* boxmot_hip_ingest_create_nv12(int n_slots, int n_streams, const int* image_rows, const int* image_cols) {
+    BoxMOTHipIngest* h = nullptr;
+    const int ok = guard([&]() {
+        require_device();
+        if (n_slots < 2 || n_streams < 1 || !image_rows || !image_cols)
+            throw std::runtime_error("boxmot_hip: ingest ring needs >= 2 slots, >= 1 stream and a (rows, cols) per stream");
+        for (int s = 0; s < n_streams; ++s) {
+            if (image_rows[s] < 1 || image_cols[s] < 1)
+                throw std::runtime_error("boxmot_hip: ingest ring stream " + std::to_string(s) + ": frame dimensions must be positive");
+            if (image_rows[s] % 2 || image_cols[s] % 2)
+                throw std::runtime_error("boxmot_hip: ingest ring stream " + std::to_string(s) + ": NV12 frames have even rows and cols, got " +
+                                         std::to_string(image_rows[s]) + " x " + std::to_string(image_cols[s]));
+        }
+        h = new BoxMOTHipIngest();
+        h->n_slots = n_slots; h->n_streams = n_streams; h->rows = image_rows[0]; h->cols = image_cols[0];
+        h->format = 1;
+        h->srows.assign(image_rows, image_rows + n_streams); h->scols.assign(image_cols, image_cols + n_streams);
+        h->offs.assign((size_t)n_streams + 1, 0);
+        h->nv_offs.assign((size_t)n_streams + 1, 0);
+        for (int s = 0; s < n_streams; ++s) {
+            const size_t px = (size_t)image_rows[s] * image_cols[s];
+            h->offs[s + 1] = (h->offs[s] + px * 3 + 255) / 256 * 256;
+            h->nv_offs[s + 1] = (h->nv_offs[s] + px * 3 / 2 + 255) / 256 * 256;
+        }
+        ingest_build(h);
+    });
+    if (!ok) { delete h; return nullptr; }
+    return h;
+}
+
+int boxmot_hip_ingest_format(BoxMOTHipIngest* handle) { return handle ? handle->format : -1; }
 
 void boxmot_hip_ingest_destroy(BoxMOTHipIngest* handle) { destroy_on(handle); }
 
@@ -2653,7 +2720,7 @@ uint8_t* boxmot_hip_ingest_host_ptr(BoxMOTHipIngest* handle, int slot, int strea
     guard_on(handle, [&]() {
         ingest_slot(handle, slot);
         if (stream < 0 || stream >= handle->n_streams) throw std::runtime_error("boxmot_hip: stream index out of range");
-        p = handle->h_slot[slot] + handle->offs[stream];
+        p = handle->h_slot[slot] + (handle->format ? handle->nv_offs : handle->offs)[stream];
     });
     return p;
 }
@@ -2670,9 +2737,72 @@ int boxmot_hip_ingest_submit(BoxMOTHipIngest* handle, int slot, int n_streams) {
         if (n_streams < 1 || n_streams > handle->n_streams) throw std::runtime_error("boxmot_hip: stream count out of range");
         // the previous consumer of this slot must be done with the device frames before they are overwritten
         if (handle->has_consumer[slot]) BM_HIP(hipStreamWaitEvent(handle->copy_stream, handle->consumed[slot], 0));
-        BM_HIP(hipMemcpyAsync(handle->d_slot[slot], handle->h_slot[slot], handle->offs[n_streams], hipMemcpyHostToDevice,
-                              handle->copy_stream));
+        if (handle->format) {           // the NV12 bytes, then their conversion into the slot's BGR frames
+            BM_HIP(hipMemcpyAsync(handle->d_nv[slot], handle->h_slot[slot], handle->nv_offs[n_streams], hipMemcpyHostToDevice,
+                                  handle->copy_stream));
+            hipLaunchKernelGGL(bm::k_nv12_to_bgr, dim3((unsigned)bm::nv12_grid_x(handle->nv_desc[slot].data(), n_streams), (unsigned)n_streams),
+                               dim3(bm::NV12_THREADS), 0, handle->copy_stream, (const bm::Nv12Desc*)handle->d_desc[slot]);
+            BM_HIP(hipGetLastError());
+        } else {
+            BM_HIP(hipMemcpyAsync(handle->d_slot[slot], handle->h_slot[slot], handle->offs[n_streams], hipMemcpyHostToDevice,
+                                  handle->copy_stream));
+        }
         BM_HIP(hipEventRecord(handle->uploaded[slot], handle->copy_stream));
+    });
+}
+
+// NV12 surfaces that already are in device memory (a hardware decoder's output): no DMA, the conversion reads them and writes the
+// slot's BGR frames under the same consumer wait / uploaded event.  Any ring: only the device side is used.
+int boxmot_hip_ingest_submit_device_nv12(BoxMOTHipIngest* handle, int slot, int n_streams, const uint8_t* const* d_y, const uint8_t* const* d_uv,
+                                         const int* pitch_y, const int* pitch_uv) {
+    return guard_on(handle, [&]() {
+        ingest_slot(handle, slot);
+        if (n_streams < 1 || n_streams > handle->n_streams) throw std::runtime_error("boxmot_hip: stream count out of range");
+        if (!d_y || !d_uv || !pitch_y || !pitch_uv) throw std::runtime_error("boxmot_hip: null argument");
+        for (int s = 0; s < n_streams; ++s) {
+            const std::string who = "boxmot_hip: ingest ring stream " + std::to_string(s);
+            if (handle->srows[s] % 2 || handle->scols[s] % 2)
+                throw std::runtime_error(who + ": NV12 frames have even rows and cols, this stream is " + std::to_string(handle->srows[s]) + " x " +
+                                         std::to_string(handle->scols[s]));
+            if (!d_y[s] || !d_uv[s]) throw std::runtime_error(who + ": null NV12 plane");
+            if (pitch_y[s] < handle->scols[s] || pitch_uv[s] < handle->scols[s])
+                throw std::runtime_error(who + ": pitch below the " + std::to_string(handle->scols[s]) + " columns of the frame");
+        }
+        if (handle->h_ext.empty()) {
+            handle->ext_used.assign(handle->n_slots, 0);
+            for (int k = 0; k < handle->n_slots; ++k) {
+                void *hp = nullptr, *dp = nullptr;
+                BM_HIP(hipHostMalloc(&hp, handle->n_streams * sizeof(bm::Nv12Desc), hipHostMallocDefault));
+                handle->h_ext.push_back(static_cast<bm::Nv12Desc*>(hp));
+                BM_HIP(hipMalloc(&dp, handle->n_streams * sizeof(bm::Nv12Desc)));
+                handle->d_ext.push_back(static_cast<bm::Nv12Desc*>(dp));
+            }
+        }
+        // the slot's pinned descriptor staging is rewritten: its previous copy must have left it (long done in a ring that is cycled)
+        if (handle->ext_used[slot]) BM_HIP(hipEventSynchronize(handle->uploaded[slot]));
+        bm::Nv12Desc* desc = handle->h_ext[slot];
+        for (int s = 0; s < n_streams; ++s)
+            desc[s] = bm::Nv12Desc{d_y[s], d_uv[s], pitch_y[s], pitch_uv[s], handle->srows[s], handle->scols[s], handle->d_slot[slot] + handle->offs[s]};
+        const int gx = bm::nv12_grid_x(desc, n_streams);
+        if (handle->has_consumer[slot]) BM_HIP(hipStreamWaitEvent(handle->copy_stream, handle->consumed[slot], 0));
+        BM_HIP(hipMemcpyAsync(handle->d_ext[slot], desc, n_streams * sizeof(bm::Nv12Desc), hipMemcpyHostToDevice, handle->copy_stream));
+        handle->ext_used[slot] = 1;
+        hipLaunchKernelGGL(bm::k_nv12_to_bgr, dim3((unsigned)gx, (unsigned)n_streams), dim3(bm::NV12_THREADS), 0, handle->copy_stream,
+                           (const bm::Nv12Desc*)handle->d_ext[slot]);
+        BM_HIP(hipGetLastError());
+        BM_HIP(hipEventRecord(handle->uploaded[slot], handle->copy_stream));
+    });
+}
+
+// test / utility access: the slot's BGR device frame of `stream` (rows x cols x 3 bytes) once its upload is done
+int boxmot_hip_ingest_download(BoxMOTHipIngest* handle, int slot, int stream, uint8_t* out) {
+    return guard_on(handle, [&]() {
+        ingest_slot(handle, slot);
+        if (stream < 0 || stream >= handle->n_streams) throw std::runtime_error("boxmot_hip: stream index out of range");
+        if (!out) throw std::runtime_error("boxmot_hip: null argument");
+        BM_HIP(hipEventSynchronize(handle->uploaded[slot]));
+        BM_HIP(hipMemcpy(out, handle->d_slot[slot] + handle->offs[stream], (size_t)handle->srows[stream] * handle->scols[stream] * 3,
+                         hipMemcpyDeviceToHost));
     });
 }
 

@@ -323,6 +323,19 @@ int boxmot_hip_sof_debug_map(BoxMOTHipSof* handle, int stream, int which, void* 
  *   device_frames(slot)      device table of per-stream frame pointers = the d_frames argument of *_step_device[_frames]
  *   release(slot, stream)    marks the slot consumed once the work queued on `stream` so far is done; the next submit waits for it
  *   host_done(slot)          blocks until the slot's upload has left the host buffer (only needed before refilling it)
+ * NV12 rings (create_nv12; format() = 1): decoders hand out NV12 -- a rows x cols Y plane followed by a rows/2 x cols plane of
+ * interleaved (U, V) pairs, 1.5 bytes per pixel -- so the host slots hold NV12 and submit moves half the bytes:
+ *   host_ptr(slot, stream)   where the caller writes the stream's NV12 frame, tightly packed (pitch = cols, UV directly after Y)
+ *   submit(slot, n)          the H2D copy of the first n streams' NV12 bytes, then one kernel on the copy stream that converts them
+ *                            into the slot's BGR device frames (COLOR_YUV2BGR_NV12: BT.601 limited range, 20-bit fixed point)
+ *   wait / device_frames / release / host_done are unchanged: everything downstream reads the same BGR frames.
+ * submit_device_nv12(slot, n, d_y, d_uv, pitch_y, pitch_uv) takes NV12 surfaces that already are in device memory (host arrays of
+ * n device pointers and byte pitches >= cols): no DMA, the conversion reads the surfaces and writes the slot's BGR frames under the
+ * same consumer wait and "uploaded" event.  It works on any ring whose streams have even sizes (BGR rings included: only the device
+ * side is used).  The surfaces must be COMPLETE when the call is made -- the ring orders the conversion after the slot's consumer,
+ * not after the decoder; synchronise with the decoder first -- and stay untouched until wait()'s stream has passed the slot.
+ * download(slot, stream, out) is a test / utility entry: it blocks for the slot's upload and copies the stream's rows x cols x 3
+ * BGR device frame to `out`.
  * ------------------------------------------------------------------------------------------------ */
 typedef struct BoxMOTHipIngest BoxMOTHipIngest;
 BoxMOTHipIngest* boxmot_hip_ingest_create(int n_slots, int n_streams, int image_rows, int image_cols);
@@ -336,6 +349,12 @@ int boxmot_hip_ingest_submit(BoxMOTHipIngest* handle, int slot, int n_streams);
 int boxmot_hip_ingest_wait(BoxMOTHipIngest* handle, int slot, void* consumer_hip_stream);
 int boxmot_hip_ingest_release(BoxMOTHipIngest* handle, int slot, void* consumer_hip_stream);
 int boxmot_hip_ingest_host_done(BoxMOTHipIngest* handle, int slot);
+/* NV12 ring: image sizes per stream (a uniform ring passes equal entries); odd rows or cols is an error that names the stream */
+BoxMOTHipIngest* boxmot_hip_ingest_create_nv12(int n_slots, int n_streams, const int* image_rows, const int* image_cols);
+int boxmot_hip_ingest_submit_device_nv12(BoxMOTHipIngest* handle, int slot, int n_streams, const uint8_t* const* d_y, const uint8_t* const* d_uv,
+                                         const int* pitch_y, const int* pitch_uv);
+int boxmot_hip_ingest_format(BoxMOTHipIngest* handle);       /* 0: BGR host slots, 1: NV12 host slots */
+int boxmot_hip_ingest_download(BoxMOTHipIngest* handle, int slot, int stream, uint8_t* out);
 
 /* ------------------------------------------------------------------------------------------------
  * DeepOCSORT (boxmot/trackers/bbox/deepocsort/deepocsort.py:235-492).  The reference has no native backend

@@ -1,9 +1,12 @@
 """PCIe-inclusive throughput of the drop-in host API (development tool): every update hands over host buffers --
 detections and a fresh 1080p uint8 frame per stream -- and reads the rows back, ReID inside update.
 
-    python tools/host_api_bench.py [--streams S] [--steps K]
+    python tools/host_api_bench.py [--streams S] [--steps K] [--nv12]
 
-Two numbers: ``update()`` of a single-stream BotSort (the reference-shaped call) and ``update_batch`` of S streams."""
+Two numbers: ``update()`` of a single-stream BotSort (the reference-shaped call) and ``update_batch`` of S streams (host frames per
+call, and through the pinned ingest ring).  ``--nv12`` adds the same ring loop through an NV12 ring (half the PCIe bytes, converted
+to BGR on the device): the frames then ARE an NV12 source and the BGR lines use its reference conversion (tests/nv12_ref.py), so all
+the lines track the same pictures."""
 import argparse
 import json
 import sys
@@ -21,6 +24,7 @@ def main():
     ap.add_argument("--streams", type=int, default=16)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=6)
+    ap.add_argument("--nv12", action="store_true", help="also run the ring loop through an NV12 ring")
     a = ap.parse_args()
     from boxmot_amd.botsort import BotSort
     from boxmot_amd.reid import HipReID
@@ -49,6 +53,12 @@ def main():
     scs = [Scenario(64, 256, stream=s) for s in range(S)]
     dets = [[scs[s].frame(t, with_embs=False)[0] for s in range(S)] for t in range(T)]
     imgs = [scs[s].image for s in range(S)]
+    nv = None
+    if a.nv12:
+        sys.path.insert(0, str(ROOT / "tests"))
+        import nv12_ref
+        nv = [nv12_ref.bgr_to_nv12(im) for im in imgs]
+        imgs = [nv12_ref.nv12_to_bgr(f, im.shape[0] // 2 * 2, im.shape[1] // 2 * 2) for f, im in zip(nv, imgs)]
     ms = MultiStreamBotSort(S, max_tracks=512, max_dets=256, emb_dim=512, reid_weights=sd, **kw)
     ms.set_reid_mode(1)
     for t in range(a.warmup):
@@ -77,6 +87,25 @@ def main():
     print(json.dumps({"api": f"update_batch via FrameRing ({S} streams, pinned host slots, upload of t+1 overlapped with tracking of t)",
                       "frames_per_s": S * a.steps / dtr, "ms_per_step": 1e3 * dtr / a.steps, "h2d_mb_per_step": mb}), flush=True)
     ring.close()
+    if nv is not None:
+        ms.reset()
+        ring = FrameRing(3, S, imgs[0].shape[0], imgs[0].shape[1], fmt="nv12")
+        stack = np.stack(nv)
+        for k in range(3):
+            ring.host_view(k)[...] = stack
+        ring.submit(0)
+        t_nv = 0.0
+        for t in range(T):
+            if t == a.warmup:
+                t_nv = time.perf_counter()
+            k, k1 = t % 3, (t + 1) % 3
+            ring.submit(k1)                              # NV12 upload + conversion of frame t + 1 on the copy stream ...
+            ms.update_batch(dets[t], ring=ring, slot=k)  # ... while frame t is tracked
+        dtn = time.perf_counter() - t_nv
+        print(json.dumps({"api": f"update_batch via FrameRing fmt=nv12 ({S} streams, pinned NV12 host slots, upload + device conversion of t+1 overlapped "
+                                 "with tracking of t)", "frames_per_s": S * a.steps / dtn, "ms_per_step": 1e3 * dtn / a.steps,
+                          "h2d_mb_per_step": S * nv[0].nbytes / 1e6}), flush=True)
+        ring.close()
     print(json.dumps({"api": f"update_batch ({S} streams, one 1080p frame per stream uploaded per step)", "frames_per_s": S * a.steps / dt,
                       "ms_per_step": 1e3 * dt / a.steps, "h2d_mb_per_step": mb, "h2d_gb_per_s_if_only_copy": mb / (1e3 * dt / a.steps)}), flush=True)
 
