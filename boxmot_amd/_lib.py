@@ -109,6 +109,13 @@ class StrongSortConfig(ctypes.Structure):
     ]
 
 
+class Letterbox(ctypes.Structure):
+    """``BoxMOTHipLetterbox`` (include/boxmot_hip.h)."""
+
+    _fields_ = [("out_rows", ctypes.c_int), ("out_cols", ctypes.c_int), ("mode", ctypes.c_int), ("dtype", ctypes.c_int),
+                ("rgb", ctypes.c_int), ("unit", ctypes.c_int), ("pad_value", ctypes.c_int)]
+
+
 # every symbol include/boxmot_hip.h declares: (name, restype, argtypes)
 _VP = ctypes.c_void_p
 _I = ctypes.c_int
@@ -223,6 +230,8 @@ SIGNATURES = {
     "boxmot_hip_ingest_submit_device_nv12": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP]),
     "boxmot_hip_ingest_format": (_I, [_VP]),
     "boxmot_hip_ingest_download": (_I, [_VP, _I, _I, _VP]),
+    "boxmot_hip_letterbox_geometry": (_I, [_I, _I, ctypes.POINTER(Letterbox), c_double_p]),
+    "boxmot_hip_ingest_letterbox": (_I, [_VP, _I, _I, ctypes.POINTER(Letterbox), _VP, _VP]),
     "boxmot_hip_last_error": (ctypes.c_char_p, []),
     "boxmot_hip_device_count": (_I, []),
     "boxmot_hip_botsort_device": (_I, [_VP]),

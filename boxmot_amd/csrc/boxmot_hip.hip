@@ -23,6 +23,7 @@
 #include "cmc_ecc.hpp"
 #include "cmc_sof.hpp"
 #include "ingest_nv12.hpp"
+#include "ingest_letterbox.hpp"
 
 namespace {
 
@@ -332,8 +333,17 @@ struct BoxMOTHipIngest : DeviceBound {
     std::vector<char> ext_used;
     std::vector<hipEvent_t> uploaded, consumed;
     std::vector<char> has_consumer;
+    // letterbox (csrc/ingest_letterbox.hpp); all of it is made by the first boxmot_hip_ingest_letterbox call, none by a ring that never calls it
+    struct LetterboxTable { int H, W, mode; std::vector<bm::LetterboxGeom> geom; std::vector<char> ok; bm::LetterboxGeom* d_geom; };
+    std::vector<LetterboxTable> lb_tables;          // per (H, W, mode): the streams' geometry, on the host and on the device
+    uint32_t* d_lb_lut[4] = {nullptr, nullptr, nullptr, nullptr};      // [2 * unit + dtype]: the 256 table entries
+    std::vector<hipEvent_t> lb_done;                // [n_slots]: the slot's last letterbox launch
+    std::vector<char> has_lb;
     ~BoxMOTHipIngest() {
         if (copy_stream) (void)hipStreamSynchronize(copy_stream);
+        for (auto e : lb_done) { (void)hipEventSynchronize(e); (void)hipEventDestroy(e); }
+        for (auto& t : lb_tables) if (t.d_geom) (void)hipFree(t.d_geom);
+        for (auto p : d_lb_lut) if (p) (void)hipFree(p);
         for (auto p : h_slot) if (p) (void)hipHostFree(p);
         for (auto p : d_slot) if (p) (void)hipFree(p);
         for (auto p : d_nv) if (p) (void)hipFree(p);
@@ -2715,6 +2725,12 @@ static void ingest_slot(BoxMOTHipIngest* h, int slot) {
     if (slot < 0 || slot >= h->n_slots) throw std::runtime_error("boxmot_hip: ingest slot out of range");
 }
 
+// a letterbox launch that reads the slot's frames (boxmot_hip_ingest_letterbox) must be done before they are overwritten; a ring
+// that never letterboxes has no such event and makes no call here
+static void ingest_wait_letterbox(BoxMOTHipIngest* h, int slot) {
+    if (!h->has_lb.empty() && h->has_lb[slot]) BM_HIP(hipStreamWaitEvent(h->copy_stream, h->lb_done[slot], 0));
+}
+
 uint8_t* boxmot_hip_ingest_host_ptr(BoxMOTHipIngest* handle, int slot, int stream) {
     uint8_t* p = nullptr;
     guard_on(handle, [&]() {
@@ -2737,6 +2753,7 @@ int boxmot_hip_ingest_submit(BoxMOTHipIngest* handle, int slot, int n_streams) {
         if (n_streams < 1 || n_streams > handle->n_streams) throw std::runtime_error("boxmot_hip: stream count out of range");
         // the previous consumer of this slot must be done with the device frames before they are overwritten
         if (handle->has_consumer[slot]) BM_HIP(hipStreamWaitEvent(handle->copy_stream, handle->consumed[slot], 0));
+        ingest_wait_letterbox(handle, slot);
         if (handle->format) {           // the NV12 bytes, then their conversion into the slot's BGR frames
             BM_HIP(hipMemcpyAsync(handle->d_nv[slot], handle->h_slot[slot], handle->nv_offs[n_streams], hipMemcpyHostToDevice,
                                   handle->copy_stream));
@@ -2785,6 +2802,7 @@ int boxmot_hip_ingest_submit_device_nv12(BoxMOTHipIngest* handle, int slot, int 
             desc[s] = bm::Nv12Desc{d_y[s], d_uv[s], pitch_y[s], pitch_uv[s], handle->srows[s], handle->scols[s], handle->d_slot[slot] + handle->offs[s]};
         const int gx = bm::nv12_grid_x(desc, n_streams);
         if (handle->has_consumer[slot]) BM_HIP(hipStreamWaitEvent(handle->copy_stream, handle->consumed[slot], 0));
+        ingest_wait_letterbox(handle, slot);
         BM_HIP(hipMemcpyAsync(handle->d_ext[slot], desc, n_streams * sizeof(bm::Nv12Desc), hipMemcpyHostToDevice, handle->copy_stream));
         handle->ext_used[slot] = 1;
         hipLaunchKernelGGL(bm::k_nv12_to_bgr, dim3((unsigned)gx, (unsigned)n_streams), dim3(bm::NV12_THREADS), 0, handle->copy_stream,
@@ -2825,6 +2843,107 @@ int boxmot_hip_ingest_host_done(BoxMOTHipIngest* handle, int slot) {
     return guard_on(handle, [&]() {
         ingest_slot(handle, slot);
         BM_HIP(hipEventSynchronize(handle->uploaded[slot]));       // the host buffer of the slot may be refilled
+    });
+}
+
+// ---- letterboxed detector input from a slot (csrc/ingest_letterbox.hpp has the definition) ----
+static void letterbox_check_config(const BoxMOTHipLetterbox* cfg) {
+    if (!cfg) throw std::runtime_error("boxmot_hip: null letterbox config");
+    if (cfg->out_rows < 1 || cfg->out_cols < 1) throw std::runtime_error("boxmot_hip: letterbox output size must be positive");
+    if (cfg->mode != 0 && cfg->mode != 1) throw std::runtime_error("boxmot_hip: unknown letterbox mode " + std::to_string(cfg->mode) + " (0 center, 1 topleft)");
+}
+
+int boxmot_hip_letterbox_geometry(int image_rows, int image_cols, const BoxMOTHipLetterbox* cfg, double* out) {
+    return guard([&]() {
+        letterbox_check_config(cfg);
+        if (!out) throw std::runtime_error("boxmot_hip: null argument");
+        if (image_rows < 1 || image_cols < 1) throw std::runtime_error("boxmot_hip: frame dimensions must be positive");
+        bm::LetterboxGeom g;
+        const bool ok = bm::letterbox_geometry(image_rows, image_cols, cfg->out_rows, cfg->out_cols, cfg->mode, &out[0], &g);
+        out[1] = g.new_w; out[2] = g.new_h; out[3] = g.top; out[4] = g.left;
+        if (!ok)
+            throw std::runtime_error("boxmot_hip: letterbox of a " + std::to_string(image_rows) + " x " + std::to_string(image_cols) + " frame into " +
+                                     std::to_string(cfg->out_rows) + " x " + std::to_string(cfg->out_cols) + " leaves no picture (" +
+                                     std::to_string(g.new_h) + " x " + std::to_string(g.new_w) + ")");
+    });
+}
+
+// fp32 -> fp16 bits, round to nearest even, for the table's values (0 or a normal fp16: 1 / 255 .. 255)
+static uint32_t letterbox_half_bits(float f) {
+    uint32_t x;
+    std::memcpy(&x, &f, 4);
+    if (x == 0) return 0;
+    uint32_t h = ((((x >> 23) & 255u) - 127u + 15u) << 10) | ((x & 0x7fffffu) >> 13);
+    const uint32_t rem = x & 0x1fffu;
+    if (rem > 0x1000u || (rem == 0x1000u && (h & 1u))) h += 1;             // (a carry out of the mantissa raises the exponent)
+    return h;
+}
+
+int boxmot_hip_ingest_letterbox(BoxMOTHipIngest* handle, int slot, int n_streams, const BoxMOTHipLetterbox* cfg, void* d_out,
+                                void* consumer_hip_stream) {
+    return guard_on(handle, [&]() {
+        ingest_slot(handle, slot);
+        if (n_streams < 1 || n_streams > handle->n_streams) throw std::runtime_error("boxmot_hip: stream count out of range");
+        letterbox_check_config(cfg);
+        if (cfg->dtype != 0 && cfg->dtype != 1) throw std::runtime_error("boxmot_hip: unknown letterbox dtype " + std::to_string(cfg->dtype) + " (0 fp32, 1 fp16)");
+        if (cfg->out_cols % bm::LB_PX) throw std::runtime_error("boxmot_hip: letterbox out_cols must be a multiple of 8, got " + std::to_string(cfg->out_cols));
+        if (cfg->pad_value < 0 || cfg->pad_value > 255) throw std::runtime_error("boxmot_hip: letterbox pad_value must be within 0..255, got " + std::to_string(cfg->pad_value));
+        if (!d_out) throw std::runtime_error("boxmot_hip: null letterbox output");
+        if ((uintptr_t)d_out & 15) throw std::runtime_error("boxmot_hip: the letterbox output must be 16-byte aligned");
+        const int H = cfg->out_rows, W = cfg->out_cols;
+        // the streams' geometry for this (H, W, mode): computed and copied to the device once, so a steady-state call copies nothing
+        BoxMOTHipIngest::LetterboxTable* tab = nullptr;
+        for (auto& t : handle->lb_tables) if (t.H == H && t.W == W && t.mode == cfg->mode) tab = &t;
+        if (!tab) {
+            if (handle->lb_tables.size() >= 16) {           // a caller that keeps changing the size: drop the oldest (hipFree waits for the device)
+                BM_HIP(hipFree(handle->lb_tables.front().d_geom));
+                handle->lb_tables.erase(handle->lb_tables.begin());
+            }
+            BoxMOTHipIngest::LetterboxTable t{H, W, cfg->mode, {}, {}, nullptr};
+            t.geom.resize(handle->n_streams); t.ok.resize(handle->n_streams);
+            for (int s = 0; s < handle->n_streams; ++s)
+                t.ok[s] = bm::letterbox_geometry(handle->srows[s], handle->scols[s], H, W, cfg->mode, nullptr, &t.geom[s]) ? 1 : 0;
+            void* dp = nullptr;
+            BM_HIP(hipMalloc(&dp, handle->n_streams * sizeof(bm::LetterboxGeom)));
+            t.d_geom = static_cast<bm::LetterboxGeom*>(dp);
+            handle->lb_tables.push_back(std::move(t));
+            tab = &handle->lb_tables.back();
+            BM_HIP(hipMemcpy(dp, tab->geom.data(), handle->n_streams * sizeof(bm::LetterboxGeom), hipMemcpyHostToDevice));
+        }
+        for (int s = 0; s < n_streams; ++s)
+            if (!tab->ok[s])
+                throw std::runtime_error("boxmot_hip: ingest ring stream " + std::to_string(s) + ": letterbox of a " + std::to_string(handle->srows[s]) +
+                                         " x " + std::to_string(handle->scols[s]) + " frame into " + std::to_string(H) + " x " + std::to_string(W) +
+                                         " leaves no picture (" + std::to_string(tab->geom[s].new_h) + " x " + std::to_string(tab->geom[s].new_w) + ")");
+        const int which = 2 * (cfg->unit ? 1 : 0) + cfg->dtype;
+        if (!handle->d_lb_lut[which]) {
+            uint32_t lut[256];
+            for (int v = 0; v < 256; ++v) {
+                const float f = cfg->unit ? (float)v / 255.0f : (float)v;
+                if (cfg->dtype) lut[v] = letterbox_half_bits(f);
+                else std::memcpy(&lut[v], &f, 4);
+            }
+            void* lp = nullptr;
+            BM_HIP(hipMalloc(&lp, sizeof(lut)));
+            handle->d_lb_lut[which] = static_cast<uint32_t*>(lp);
+            BM_HIP(hipMemcpy(lp, lut, sizeof(lut), hipMemcpyHostToDevice));
+        }
+        if (handle->lb_done.empty()) {
+            for (int k = 0; k < handle->n_slots; ++k) {
+                hipEvent_t e;
+                BM_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+                handle->lb_done.push_back(e);
+            }
+            handle->has_lb.assign(handle->n_slots, 0);
+        }
+        hipStream_t st = static_cast<hipStream_t>(consumer_hip_stream);
+        BM_HIP(hipStreamWaitEvent(st, handle->uploaded[slot], 0));
+        hipLaunchKernelGGL(bm::k_letterbox, dim3((unsigned)bm::letterbox_grid_x(H, W), (unsigned)n_streams), dim3(bm::LB_THREADS), 0, st,
+                           (const uint8_t* const*)handle->d_ptrs[slot], (const bm::LetterboxGeom*)tab->d_geom, (const uint32_t*)handle->d_lb_lut[which],
+                           d_out, H, W, cfg->dtype, cfg->rgb ? 1 : 0, cfg->pad_value);
+        BM_HIP(hipGetLastError());
+        BM_HIP(hipEventRecord(handle->lb_done[slot], st));
+        handle->has_lb[slot] = 1;
     });
 }
 

@@ -22,16 +22,84 @@ host -- and converts them into the same BGR device frames with one kernel behind
     ring.host_view(k, s)[...] = nv12 frame, (rows * 3 // 2, cols) uint8 ; ring.submit(k)
     ring.submit_device_nv12(k, y_ptrs, uv_ptrs, pitch_y, pitch_uv)      # surfaces a hardware decoder left in HBM (any ring)
 
+The consumer that runs before the tracker is the caller's detector.  ``letterbox`` writes its input -- letterboxed, planar,
+normalised fp16 / fp32, the form every YOLO-family detector takes -- for all streams of a slot with one kernel on the detector's
+stream, straight from the slot's device frames (no second host copy, no second upload); ``LetterboxGeometry.to_frame`` maps the
+detector's boxes back to frame coordinates:
+
+    x = torch.empty((S, 3, 640, 640), dtype=torch.float16, device="cuda")
+    geo = ring.letterbox(k, x, hip_stream=torch.cuda.current_stream().cuda_stream)
+    dets = [g.to_frame(d) for g, d in zip(geo, my_detector(x))]       # the caller's detector and NMS
+    rows = tracker.update_batch(dets, ring=ring, slot=k)
+
 Everything is a thin ctypes wrapper over boxmot_hip_ingest_* (include/boxmot_hip.h).
 """
 from __future__ import annotations
 
 import ctypes
 import sys
+from typing import NamedTuple
 
 import numpy as np
 
 from boxmot_amd import _lib
+
+LETTERBOX_MODES = {"center": 0, "topleft": 1}
+
+
+class LetterboxGeometry(NamedTuple):
+    """Where a (rows, cols) frame lies inside an (H, W) letterboxed tensor: it is resized by ``gain`` to (new_h, new_w) and placed
+    with its corner at (top, left).  ``rows, cols`` is the frame size itself (what ``to_frame`` clips to)."""
+    gain: float
+    new_w: int
+    new_h: int
+    top: int
+    left: int
+    rows: int = 0
+    cols: int = 0
+
+    def to_frame(self, boxes) -> np.ndarray:
+        """Detector-space ``xyxy`` (columns 0..3 of an (N, >= 4) table) -> frame coordinates: ``((x - left) / gain, (y - top) /
+        gain)`` clipped to ``[0, cols]`` and ``[0, rows]``, in float32.  Other columns are untouched; the input is not modified."""
+        b = np.array(boxes, dtype=np.float32, ndmin=2)
+        if b.shape[-1] < 4:
+            raise ValueError(f"to_frame: boxes need at least the 4 xyxy columns, got shape {b.shape}")
+        gain = np.float32(self.gain)
+        b[:, [0, 2]] = np.clip((b[:, [0, 2]] - np.float32(self.left)) / gain, np.float32(0), np.float32(self.cols))
+        b[:, [1, 3]] = np.clip((b[:, [1, 3]] - np.float32(self.top)) / gain, np.float32(0), np.float32(self.rows))
+        return b
+
+
+def _letterbox_size(size):
+    if isinstance(size, (int, np.integer)):
+        size = (size, size)
+    size = tuple(int(v) for v in size)
+    if len(size) != 2 or size[0] < 1 or size[1] < 1:
+        raise ValueError(f"letterbox: size must be a positive (H, W), got {size}")
+    return size
+
+
+def letterbox_geometry(rows: int, cols: int, size, mode: str = "center") -> LetterboxGeometry:
+    """The geometry ``FrameRing.letterbox`` uses for a (rows, cols) frame and an output ``size`` (H, W) -- equal to
+    ``boxmot_hip_letterbox_geometry``.  ``mode="center"``: Ultralytics ``LetterBox(auto=False, scaleup=True, center=True)`` (sizes
+    rounded half-to-even, an odd padding puts the extra line at the bottom / right); ``mode="topleft"``: YOLOX ``preproc`` (sizes
+    truncated, picture in the top left corner).  A picture that would vanish (new size < 1) raises ``ValueError``."""
+    rows, cols = int(rows), int(cols)
+    H, W = _letterbox_size(size)
+    if mode not in LETTERBOX_MODES:
+        raise ValueError(f"letterbox: unknown mode {mode!r} (\"center\" or \"topleft\")")
+    if rows < 1 or cols < 1:
+        raise ValueError(f"letterbox: frame dimensions must be positive, got {(rows, cols)}")
+    gain = min(H / rows, W / cols)
+    if mode == "center":
+        new_w, new_h = round(cols * gain), round(rows * gain)
+        top, left = round((H - new_h) / 2 - 0.1), round((W - new_w) / 2 - 0.1)
+    else:
+        new_w, new_h = int(cols * gain), int(rows * gain)
+        top = left = 0
+    if new_w < 1 or new_h < 1:
+        raise ValueError(f"letterbox of a {rows} x {cols} frame into {H} x {W} leaves no picture ({new_h} x {new_w})")
+    return LetterboxGeometry(gain, new_w, new_h, top, left, rows, cols)
 
 
 class FrameRing:
@@ -172,6 +240,48 @@ class FrameRing:
         out = np.empty((r, c, 3), dtype=np.uint8)
         _lib.check(self._lib.boxmot_hip_ingest_download(self._handle, int(slot), stream, out.ctypes.data))
         return out
+
+    def letterbox(self, slot: int, out, size=None, mode: str = "center", rgb: bool = True, unit: bool = True, pad: int = 114,
+                  n_streams: int | None = None, hip_stream: int = 0):
+        """Write the letterboxed detector input of the slot's first ``n_streams`` streams (default: all) into ``out``: a contiguous
+        float16 / float32 device tensor of shape (N, 3, H, W), N >= n_streams, on the ring's device -- anything with ``data_ptr()``,
+        ``dtype``, ``shape`` and ``is_contiguous()``; rows beyond ``n_streams`` are left alone.  ``size`` (H, W) defaults to
+        ``out.shape[-2:]``; W must be a multiple of 8.  ``mode`` as ``letterbox_geometry``; plane order RGB (``rgb=True``,
+        Ultralytics) or BGR (YOLOX); values ``v / 255`` (``unit=True``) or ``v``; ``pad``: the byte outside the picture.
+        The kernel runs on ``hip_stream`` after the slot's upload (no host wait), so work queued there afterwards -- the
+        detector -- sees the tensor; the slot's next ``submit`` waits for it.  Returns the streams' ``LetterboxGeometry``."""
+        n = self.n_streams if n_streams is None else int(n_streams)
+        if not 1 <= n <= self.n_streams:
+            raise ValueError(f"letterbox: n_streams {n} out of range for a ring of {self.n_streams} streams")
+        if mode not in LETTERBOX_MODES:
+            raise ValueError(f"letterbox: unknown mode {mode!r} (\"center\" or \"topleft\")")
+        shape = tuple(int(v) for v in out.shape)
+        H, W = _letterbox_size(shape[-2:] if size is None else size)
+        if len(shape) != 4 or shape[0] < n or shape[1:] != (3, H, W):
+            raise ValueError(f"letterbox: out must have shape (N >= {n}, 3, {H}, {W}), got {shape}")
+        dtype = {"float32": 0, "float16": 1}.get(str(out.dtype).split(".")[-1])
+        if dtype is None:
+            raise ValueError(f"letterbox: out must be float16 or float32, got {out.dtype}")
+        if not out.is_contiguous():
+            raise ValueError("letterbox: out must be contiguous")
+        if W % 8:
+            raise ValueError(f"letterbox: the output width must be a multiple of 8, got {W}")
+        pad = int(pad)
+        if not 0 <= pad <= 255:
+            raise ValueError(f"letterbox: pad must be within 0..255, got {pad}")
+        ptr = int(out.data_ptr())
+        if not ptr or ptr % 16:
+            raise ValueError(f"letterbox: out must be a non-null 16-byte aligned device address, got {ptr:#x}")
+        geo = []
+        for s in range(n):
+            try:
+                geo.append(letterbox_geometry(*self.sizes[s], (H, W), mode))
+            except ValueError as e:
+                raise ValueError(f"stream {s}: {e}") from None
+        cfg = _lib.Letterbox(H, W, LETTERBOX_MODES[mode], dtype, int(bool(rgb)), int(bool(unit)), pad)
+        _lib.check(self._lib.boxmot_hip_ingest_letterbox(self._handle, int(slot), n, ctypes.byref(cfg), ctypes.c_void_p(ptr),
+                                                         ctypes.c_void_p(int(hip_stream))))
+        return geo
 
     def wait(self, slot: int, consumer_stream: int) -> None:
         _lib.check(self._lib.boxmot_hip_ingest_wait(self._handle, int(slot), ctypes.c_void_p(consumer_stream)))

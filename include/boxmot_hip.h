@@ -356,6 +356,24 @@ int boxmot_hip_ingest_submit_device_nv12(BoxMOTHipIngest* handle, int slot, int 
 int boxmot_hip_ingest_format(BoxMOTHipIngest* handle);       /* 0: BGR host slots, 1: NV12 host slots */
 int boxmot_hip_ingest_download(BoxMOTHipIngest* handle, int slot, int stream, uint8_t* out);
 
+/* Letterboxed detector input from a slot (csrc/ingest_letterbox.hpp has the full definition): the first n_streams BGR frames of the
+ * slot -> d_out, planar (n_streams, 3, out_rows, out_cols) fp32 or fp16, contiguous.  Per stream: gain = min(out_rows / rows,
+ * out_cols / cols); mode 0 "center" (Ultralytics LetterBox): new size = round(size * gain), top / left = floor of half the padding;
+ * mode 1 "topleft" (YOLOX preproc): new size = int(size * gain), top = left = 0; the picture is cv2.resize(INTER_LINEAR) as the
+ * crop kernels restate it, the rest is pad_value (0..255, usually 114); plane p is source channel 2 - p (rgb) or p; a byte v
+ * becomes float32(v) / float32(255) (unit; for fp16 that value rounded to nearest even) or v itself.  The whole block is written.
+ * out_cols must be a multiple of 8 and d_out 16-byte aligned; a stream whose picture would vanish (new size < 1) is an error that
+ * names the stream.
+ * Ordering: the call makes consumer_hip_stream wait for the slot's upload (as wait() does, no host wait), launches there -- so the
+ * detector's stream sees the tensor in order -- and records an event of its own that the next submit / submit_device_nv12 of the
+ * slot waits for before it overwrites the frames.  release() stays the tracker's.  The geometry table of an (out_rows, out_cols,
+ * mode) is built on the first call and kept on the handle: later calls copy nothing to the device.
+ * letterbox_geometry needs no handle and no device: out[5] = gain, new_w, new_h, top, left of one frame size (returns 0, with
+ * out filled, where the picture would vanish). */
+typedef struct { int out_rows, out_cols, mode /*0 center, 1 topleft*/, dtype /*0 fp32, 1 fp16*/, rgb, unit, pad_value; } BoxMOTHipLetterbox;
+int boxmot_hip_letterbox_geometry(int image_rows, int image_cols, const BoxMOTHipLetterbox* cfg, double* out);
+int boxmot_hip_ingest_letterbox(BoxMOTHipIngest* handle, int slot, int n_streams, const BoxMOTHipLetterbox* cfg, void* d_out, void* consumer_hip_stream);
+
 /* ------------------------------------------------------------------------------------------------
  * DeepOCSORT (boxmot/trackers/bbox/deepocsort/deepocsort.py:235-492).  The reference has no native backend
  * for this tracker; the entry points follow the BoT-SORT ones above (same buffer, error and ownership
