@@ -1,11 +1,12 @@
 """boxmot_amd -- MI355X-native tracker update path (BoT-SORT, ByteTrack, DeepOCSORT, OC-SORT, StrongSORT; HIP kernels behind a C ABI).
 
 Public surface (mirrors the reference's for this path):
-  BotSort, ByteTrack, DeepOcSort, OcSort, StrongSort, HipReID, TrackResults, create_tracker, MultiStreamBotSort.
+  BotSort, ByteTrack, DeepOcSort, OcSort, StrongSort, HipReID, TrackResults, create_tracker, MultiStreamBotSort, DetPost.
 """
 __version__ = "0.1.0"
 
-__all__ = ["BotSort", "ByteTrack", "DeepOcSort", "OcSort", "StrongSort", "HipReID", "TrackResults", "create_tracker", "MultiStreamBotSort"]
+__all__ = ["BotSort", "ByteTrack", "DeepOcSort", "OcSort", "StrongSort", "HipReID", "TrackResults", "create_tracker", "MultiStreamBotSort",
+           "DetPost"]
 
 
 def __getattr__(name):
@@ -36,4 +37,7 @@ def __getattr__(name):
     if name == "MultiStreamBotSort":
         from boxmot_amd.streams import MultiStreamBotSort
         return MultiStreamBotSort
+    if name == "DetPost":
+        from boxmot_amd.detpost import DetPost
+        return DetPost
     raise AttributeError(name)

@@ -109,6 +109,14 @@ class StrongSortConfig(ctypes.Structure):
     ]
 
 
+class DetPostConfig(ctypes.Structure):
+    """``BoxMOTHipDetPostConfig`` (include/boxmot_hip.h)."""
+
+    _fields_ = [("n_streams", ctypes.c_int), ("n_anchors", ctypes.c_int), ("n_classes", ctypes.c_int), ("layout", ctypes.c_int),
+                ("conf_thres", ctypes.c_float), ("iou_thres", ctypes.c_float), ("max_candidates", ctypes.c_int), ("max_det", ctypes.c_int),
+                ("agnostic", ctypes.c_int), ("class_allow", ctypes.c_void_p)]
+
+
 class Letterbox(ctypes.Structure):
     """``BoxMOTHipLetterbox`` (include/boxmot_hip.h)."""
 
@@ -232,6 +240,10 @@ SIGNATURES = {
     "boxmot_hip_ingest_download": (_I, [_VP, _I, _I, _VP]),
     "boxmot_hip_letterbox_geometry": (_I, [_I, _I, ctypes.POINTER(Letterbox), c_double_p]),
     "boxmot_hip_ingest_letterbox": (_I, [_VP, _I, _I, ctypes.POINTER(Letterbox), _VP, _VP]),
+    "boxmot_hip_detpost_create": (_VP, [ctypes.POINTER(DetPostConfig)]),
+    "boxmot_hip_detpost_destroy": (None, [_VP]),
+    "boxmot_hip_detpost_run": (_I, [_VP, _I, _VP, _I, c_double_p, _VP, _I, _VP, _VP]),
+    "boxmot_hip_detpost_counters": (_I, [_VP, _VP, _I]),
     "boxmot_hip_last_error": (ctypes.c_char_p, []),
     "boxmot_hip_device_count": (_I, []),
     "boxmot_hip_botsort_device": (_I, [_VP]),

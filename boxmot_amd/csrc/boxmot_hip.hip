@@ -24,6 +24,7 @@
 #include "cmc_sof.hpp"
 #include "ingest_nv12.hpp"
 #include "ingest_letterbox.hpp"
+#include "det_post.hpp"
 
 namespace {
 
@@ -356,6 +357,42 @@ struct BoxMOTHipIngest : DeviceBound {
         if (copy_stream) (void)hipStreamDestroy(copy_stream);
     }
 };
+
+// Detection post-processing (csrc/det_post.hpp): the handle owns the per-anchor scratch, the geometry table and the counters
+struct BoxMOTHipDetPost : DeviceBound {
+    BoxMOTHipDetPostConfig cfg{};
+    uint32_t* d_keys = nullptr;                     // [n_streams][n_anchors]
+    int* d_cls = nullptr;                           // [n_streams][n_anchors]
+    int* d_counters = nullptr;                      // [n_streams][3]
+    uint8_t* d_allow = nullptr;                     // [n_classes] or null
+    bm::DetPostGeom* d_geom = nullptr;              // [n_streams]
+    bm::DetPostGeom* h_geom[2] = {nullptr, nullptr};// pinned staging of the geometry uploads, used in turn
+    hipEvent_t geom_copied[2] = {nullptr, nullptr};
+    int geom_uploads = 0, geom_valid = 0;           // uploads so far; the streams whose device entry equals `geom`
+    std::vector<bm::DetPostGeom> geom;              // what the device table holds
+    hipEvent_t done = nullptr;                      // the last run: the next one (on any stream) and counters() wait for it
+    bool ran = false;
+    ~BoxMOTHipDetPost() {
+        if (done) { if (ran) (void)hipEventSynchronize(done); (void)hipEventDestroy(done); }
+        for (auto e : geom_copied) if (e) (void)hipEventDestroy(e);
+        for (auto p : h_geom) if (p) (void)hipHostFree(p);
+        if (d_keys) (void)hipFree(d_keys);
+        if (d_cls) (void)hipFree(d_cls);
+        if (d_counters) (void)hipFree(d_counters);
+        if (d_allow) (void)hipFree(d_allow);
+        if (d_geom) (void)hipFree(d_geom);
+    }
+};
+
+namespace {
+struct DetPostLaunch {          // detpost_launch's launcher: the kernel sequence of det_post.hpp on the caller's stream
+    hipStream_t stream;
+    template <class K, class... A>
+    void operator()(K kernel, int gx, int gy, int threads, size_t lds_bytes, A... args) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)gx, (unsigned)gy), dim3((unsigned)threads), lds_bytes, stream, args...);
+    }
+};
+}  // namespace
 
 // What the three tracker handles share on the host: the weight blob and ReID engine, the staging tables of the per-stream inputs and
 // results, the frames a host update uploads, the crop list, pending camera-motion warps, the record of the tracker's tables
@@ -2944,6 +2981,110 @@ int boxmot_hip_ingest_letterbox(BoxMOTHipIngest* handle, int slot, int n_streams
         BM_HIP(hipGetLastError());
         BM_HIP(hipEventRecord(handle->lb_done[slot], st));
         handle->has_lb[slot] = 1;
+    });
+}
+
+// ---- detection post-processing (csrc/det_post.hpp has the definition) ----
+BoxMOTHipDetPost* boxmot_hip_detpost_create(const BoxMOTHipDetPostConfig* c) {
+    BoxMOTHipDetPost* h = nullptr;
+    const int ok = guard([&]() {
+        if (!c) throw std::runtime_error("boxmot_hip: null detpost config");
+        if (c->n_streams < 1 || c->n_anchors < 1 || c->n_classes < 1)
+            throw std::runtime_error("boxmot_hip: detpost needs n_streams, n_anchors and n_classes >= 1");
+        if (c->layout != 0 && c->layout != 1) throw std::runtime_error("boxmot_hip: unknown detpost layout " + std::to_string(c->layout) + " (0 cn, 1 nc_obj)");
+        if (!(c->conf_thres >= 0.0f) || !(c->conf_thres < 1.0f)) throw std::runtime_error("boxmot_hip: detpost conf_thres must be within [0, 1)");
+        if (!(c->iou_thres >= 0.0f) || !(c->iou_thres <= 1.0f)) throw std::runtime_error("boxmot_hip: detpost iou_thres must be within [0, 1]");
+        if (c->max_candidates < bm::DP_K_MIN || c->max_candidates > bm::DP_K_MAX)
+            throw std::runtime_error("boxmot_hip: detpost max_candidates must be within 64..4096, got " + std::to_string(c->max_candidates));
+        if (c->max_det < 1) throw std::runtime_error("boxmot_hip: detpost max_det must be >= 1");
+        if ((long)c->n_streams * c->n_anchors > (1L << 30)) throw std::runtime_error("boxmot_hip: detpost n_streams * n_anchors is too large");
+        require_device();
+        h = new BoxMOTHipDetPost();
+        h->cfg = *c;
+        h->cfg.class_allow = nullptr;
+        const size_t SA = (size_t)c->n_streams * c->n_anchors;
+        void* p = nullptr;
+        BM_HIP(hipMalloc(&p, SA * sizeof(uint32_t))); h->d_keys = static_cast<uint32_t*>(p);
+        BM_HIP(hipMalloc(&p, SA * sizeof(int))); h->d_cls = static_cast<int*>(p);
+        BM_HIP(hipMalloc(&p, (size_t)c->n_streams * bm::DP_COUNTERS * sizeof(int))); h->d_counters = static_cast<int*>(p);
+        BM_HIP(hipMemset(h->d_counters, 0, (size_t)c->n_streams * bm::DP_COUNTERS * sizeof(int)));
+        BM_HIP(hipMalloc(&p, (size_t)c->n_streams * sizeof(bm::DetPostGeom))); h->d_geom = static_cast<bm::DetPostGeom*>(p);
+        for (int k = 0; k < 2; ++k) {
+            BM_HIP(hipHostMalloc(&p, (size_t)c->n_streams * sizeof(bm::DetPostGeom), hipHostMallocDefault));
+            h->h_geom[k] = static_cast<bm::DetPostGeom*>(p);
+            BM_HIP(hipEventCreateWithFlags(&h->geom_copied[k], hipEventDisableTiming));
+        }
+        h->geom.resize(c->n_streams);
+        if (c->class_allow) {
+            std::vector<uint8_t> allow(c->n_classes);
+            for (int k = 0; k < c->n_classes; ++k) allow[k] = c->class_allow[k] ? 1 : 0;
+            BM_HIP(hipMalloc(&p, allow.size())); h->d_allow = static_cast<uint8_t*>(p);
+            BM_HIP(hipMemcpy(h->d_allow, allow.data(), allow.size(), hipMemcpyHostToDevice));
+        }
+        BM_HIP(hipEventCreateWithFlags(&h->done, hipEventDisableTiming));
+        // the workgroup's LDS grows with max_candidates and passes the 64 KB a kernel may take without saying so
+        const int lds = (int)bm::detpost_lds_bytes(c->max_candidates);
+        BM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(bm::k_detpost_select<float>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        BM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(bm::k_detpost_select<_Float16>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    });
+    if (!ok) { const std::string e = g_last_error; destroy_on(h); g_last_error = e; return nullptr; }
+    return h;
+}
+
+void boxmot_hip_detpost_destroy(BoxMOTHipDetPost* handle) { destroy_on(handle); }
+
+int boxmot_hip_detpost_run(BoxMOTHipDetPost* handle, int n_streams, const void* d_pred, int dtype, const double* geom, float* d_dets,
+                           int out_stride_rows, int* d_det_rows, void* hip_stream) {
+    return guard_on(handle, [&]() {
+        if (!handle) throw std::runtime_error("boxmot_hip: null detpost handle");
+        const BoxMOTHipDetPostConfig& c = handle->cfg;
+        if (n_streams < 1 || n_streams > c.n_streams)
+            throw std::runtime_error("boxmot_hip: detpost stream count " + std::to_string(n_streams) + " out of range for a handle of " + std::to_string(c.n_streams));
+        if (!d_pred || !geom || !d_dets || !d_det_rows) throw std::runtime_error("boxmot_hip: null detpost argument");
+        if (dtype != 0 && dtype != 1) throw std::runtime_error("boxmot_hip: unknown detpost dtype " + std::to_string(dtype) + " (0 fp32, 1 fp16)");
+        if ((uintptr_t)d_pred % (dtype ? 2 : 4) || (uintptr_t)d_dets % 4 || (uintptr_t)d_det_rows % 4)
+            throw std::runtime_error("boxmot_hip: detpost device addresses must be aligned to their element size");
+        if (out_stride_rows < c.max_det)
+            throw std::runtime_error("boxmot_hip: detpost out_stride_rows " + std::to_string(out_stride_rows) + " is below max_det " + std::to_string(c.max_det));
+        std::vector<bm::DetPostGeom> g(n_streams);
+        bool same = n_streams <= handle->geom_valid;
+        for (int s = 0; s < n_streams; ++s) {
+            const double* v = geom + 5 * s;
+            if (!(v[0] > 0.0) || !std::isfinite(v[0]) || !(v[3] >= 1.0) || !(v[4] >= 1.0) || !std::isfinite(v[1]) || !std::isfinite(v[2]) ||
+                !std::isfinite(v[3]) || !std::isfinite(v[4]))
+                throw std::runtime_error("boxmot_hip: detpost stream " + std::to_string(s) + ": geometry needs gain > 0 and a frame of >= 1 x 1 (gain " +
+                                         std::to_string(v[0]) + ", rows " + std::to_string(v[3]) + ", cols " + std::to_string(v[4]) + ")");
+            g[s] = bm::DetPostGeom{(float)v[0], (float)v[1], (float)v[2], (float)v[3], (float)v[4]};
+            if (same && std::memcmp(&g[s], &handle->geom[s], sizeof(bm::DetPostGeom)) != 0) same = false;
+        }
+        hipStream_t st = static_cast<hipStream_t>(hip_stream);
+        if (handle->ran) BM_HIP(hipStreamWaitEvent(st, handle->done, 0));      // the scratch and the table are the handle's
+        if (!same) {
+            const int k = handle->geom_uploads & 1;
+            if (handle->geom_uploads >= 2) BM_HIP(hipEventSynchronize(handle->geom_copied[k]));    // (two uploads ago: long done)
+            std::memcpy(handle->h_geom[k], g.data(), n_streams * sizeof(bm::DetPostGeom));
+            BM_HIP(hipMemcpyAsync(handle->d_geom, handle->h_geom[k], n_streams * sizeof(bm::DetPostGeom), hipMemcpyHostToDevice, st));
+            BM_HIP(hipEventRecord(handle->geom_copied[k], st));
+            handle->geom_uploads += 1;
+            std::copy(g.begin(), g.end(), handle->geom.begin());
+            if (handle->geom_valid < n_streams) handle->geom_valid = n_streams;
+        }
+        bm::DetPostArgs a{d_pred, handle->d_geom, handle->d_allow, handle->d_keys, handle->d_cls, d_dets, d_det_rows, handle->d_counters,
+                          c.n_anchors, c.n_classes, c.layout, c.max_candidates, c.max_det, c.agnostic ? 1 : 0, out_stride_rows, c.conf_thres, c.iou_thres};
+        DetPostLaunch launch{st};
+        bm::detpost_launch(launch, a, n_streams, dtype);
+        BM_HIP(hipGetLastError());
+        BM_HIP(hipEventRecord(handle->done, st));
+        handle->ran = true;
+    });
+}
+
+int boxmot_hip_detpost_counters(BoxMOTHipDetPost* handle, int* out, int n_streams) {
+    return guard_on(handle, [&]() {
+        if (!handle || !out) throw std::runtime_error("boxmot_hip: null detpost argument");
+        if (n_streams < 1 || n_streams > handle->cfg.n_streams) throw std::runtime_error("boxmot_hip: detpost stream count out of range");
+        if (handle->ran) BM_HIP(hipEventSynchronize(handle->done));
+        BM_HIP(hipMemcpy(out, handle->d_counters, (size_t)n_streams * bm::DP_COUNTERS * sizeof(int), hipMemcpyDeviceToHost));
     });
 }
 

@@ -1,0 +1,171 @@
+"""Detection post-processing on the device: from a YOLO-family detector's raw prediction tensor to the ``d_dets`` / ``d_det_rows``
+block the device-resident tracker steps read, in frame coordinates, with no host round trip (boxmot_hip_detpost_*,
+include/boxmot_hip.h; the definition is at the top of csrc/det_post.hpp).  The detector stays the caller's:
+
+    post = DetPost(S, n_anchors=8400, n_classes=80, layout="cn", conf=0.25, iou=0.45, max_det=256)
+    d_dets = torch.empty((S, 256, 6), device="cuda"); d_rows = torch.empty(S, dtype=torch.int32, device="cuda")
+    geo = ring.letterbox(k, x, hip_stream=st)
+    post.run(my_detector(x), geo, d_dets, d_rows, hip_stream=st)          # confidence filter, top-K, NMS, frame coordinates
+    trk.step_device(d_dets.data_ptr(), d_rows.data_ptr(), ...)            # after the tracker's stream has waited for ``st``
+
+Stated plainly: this is greedy NMS with torchvision's IoU arithmetic in float32, ``IoU > iou`` suppresses; classes are kept apart by
+COMPARING them, not by Ultralytics' ``cls * max_wh`` coordinate offset (which rounds differently); an anchor passes on ``conf >
+conf_thres`` strictly (Ultralytics' rule, not YOLOX's ``>=``); candidates are the ``max_candidates`` best by (conf descending,
+anchor index ascending), exactly.  It is compared bit for bit with a NumPy restatement of that definition -- parity with
+torchvision or Ultralytics on real detector output is not pinned by any test.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+
+from boxmot_amd import _lib
+
+LAYOUTS = {"cn": 0, "nc_obj": 1}
+_DTYPES = {"float32": 0, "float16": 1}
+
+
+def _dtype_name(t) -> str:
+    return str(t.dtype).split(".")[-1]
+
+
+def _geometry_row(g, s):
+    """(gain, top, left, rows, cols) of a ``LetterboxGeometry`` (or of a 5-sequence in that order)"""
+    try:
+        row = (g.gain, g.top, g.left, g.rows, g.cols) if hasattr(g, "gain") else tuple(g)
+        row = tuple(float(v) for v in row)
+    except (TypeError, ValueError):
+        raise ValueError(f"stream {s}: geometry must be a LetterboxGeometry or (gain, top, left, rows, cols), got {g!r}") from None
+    if len(row) != 5:
+        raise ValueError(f"stream {s}: geometry must be a LetterboxGeometry or (gain, top, left, rows, cols), got {g!r}")
+    if not (row[0] > 0 and np.isfinite(row[0])) or row[3] < 1 or row[4] < 1:
+        raise ValueError(f"stream {s}: geometry needs gain > 0 and a frame of at least 1 x 1, got gain {row[0]}, rows {row[3]}, cols {row[4]}")
+    return row
+
+
+class DetPost:
+    def __init__(self, n_streams: int, n_anchors: int, n_classes: int, layout: str = "cn", conf: float = 0.25, iou: float = 0.45,
+                 max_det: int = 256, max_candidates: int = 1024, agnostic: bool = False, classes=None):
+        """``layout``: ``"cn"`` -- (S, 4 + n_classes, n_anchors), the Ultralytics v8 / 11 raw head, conf = the best class score --
+        or ``"nc_obj"`` -- (S, n_anchors, 5 + n_classes), the YOLOX / YOLOv5 decoded head, conf = obj * the best class score.
+        ``classes``: an optional allow-list of class indices, applied to an anchor's best class."""
+        self._handle = None
+        self._configure(n_streams, n_anchors, n_classes, layout, conf, iou, max_det, max_candidates, agnostic, classes)
+        self._lib = _lib.load()
+        allow = None
+        if self.classes is not None:
+            allow = np.zeros(self.n_classes, dtype=np.uint8)
+            allow[self.classes] = 1
+        cfg = _lib.DetPostConfig(self.n_streams, self.n_anchors, self.n_classes, LAYOUTS[self.layout], self.conf, self.iou, self.max_candidates,
+                                 self.max_det, int(self.agnostic), None if allow is None else allow.ctypes.data)
+        self._handle = self._lib.boxmot_hip_detpost_create(ctypes.byref(cfg))          # (the table is copied by the call)
+        if not self._handle:
+            raise RuntimeError(_lib.last_error())
+
+    def _configure(self, n_streams, n_anchors, n_classes, layout="cn", conf=0.25, iou=0.45, max_det=256, max_candidates=1024, agnostic=False,
+                   classes=None):
+        """the options, checked; touches neither the library nor a device"""
+        for name, v in (("n_streams", n_streams), ("n_anchors", n_anchors), ("n_classes", n_classes), ("max_det", max_det)):
+            if int(v) != v or int(v) < 1:
+                raise ValueError(f"DetPost: {name} must be an integer >= 1, got {v!r}")
+        if layout not in LAYOUTS:
+            raise ValueError(f"DetPost: unknown layout {layout!r} (\"cn\" or \"nc_obj\")")
+        if not 0.0 <= float(conf) < 1.0:
+            raise ValueError(f"DetPost: conf must be within [0, 1), got {conf!r}")
+        if not 0.0 <= float(iou) <= 1.0:
+            raise ValueError(f"DetPost: iou must be within [0, 1], got {iou!r}")
+        if int(max_candidates) != max_candidates or not 64 <= int(max_candidates) <= 4096:
+            raise ValueError(f"DetPost: max_candidates must be an integer within 64..4096, got {max_candidates!r}")
+        if classes is not None:
+            classes = [int(c) for c in classes]
+            bad = [c for c in classes if not 0 <= c < int(n_classes)]
+            if bad or not classes:
+                raise ValueError(f"DetPost: classes must be a non-empty list of indices within 0..{int(n_classes) - 1}, got {classes}")
+        self.n_streams, self.n_anchors, self.n_classes, self.layout = int(n_streams), int(n_anchors), int(n_classes), layout
+        self.conf, self.iou = float(np.float32(conf)), float(np.float32(iou))          # the thresholds are float32 on the device
+        self.max_det, self.max_candidates, self.agnostic, self.classes = int(max_det), int(max_candidates), bool(agnostic), classes
+
+    def pred_shape(self, n: int | None = None) -> tuple:
+        n = self.n_streams if n is None else n
+        return (n, 4 + self.n_classes, self.n_anchors) if self.layout == "cn" else (n, self.n_anchors, 5 + self.n_classes)
+
+    def _check_run(self, pred, geo, d_dets, d_det_rows):
+        """(n_streams, dtype code, geometry table) of a call; raises ValueError naming what is wrong"""
+        n = len(geo)
+        if not 1 <= n <= self.n_streams:
+            raise ValueError(f"DetPost.run: geo has {n} entries for a handle of {self.n_streams} streams")
+        shape = tuple(int(v) for v in pred.shape)
+        if len(shape) != 3 or shape[0] < n or shape[1:] != self.pred_shape()[1:]:
+            raise ValueError(f"DetPost.run: pred must have shape {('N >= %d' % n,) + self.pred_shape()[1:]} for layout {self.layout!r}, got {shape}")
+        dtype = _DTYPES.get(_dtype_name(pred))
+        if dtype is None:
+            raise ValueError(f"DetPost.run: pred must be float16 or float32, got {pred.dtype}")
+        if not pred.is_contiguous():
+            raise ValueError("DetPost.run: pred must be contiguous")
+        dshape = tuple(int(v) for v in d_dets.shape)
+        if len(dshape) != 3 or dshape[0] < n or dshape[2] != 6:
+            raise ValueError(f"DetPost.run: d_dets must have shape (N >= {n}, rows, 6), got {dshape}")
+        if dshape[1] < self.max_det:
+            raise ValueError(f"DetPost.run: d_dets holds {dshape[1]} rows per stream, fewer than max_det = {self.max_det}")
+        if _dtype_name(d_dets) != "float32":
+            raise ValueError(f"DetPost.run: d_dets must be float32, got {d_dets.dtype}")
+        if not d_dets.is_contiguous():
+            raise ValueError("DetPost.run: d_dets must be contiguous")
+        rshape = tuple(int(v) for v in d_det_rows.shape)
+        if len(rshape) != 1 or rshape[0] < n:
+            raise ValueError(f"DetPost.run: d_det_rows must have shape (N >= {n},), got {rshape}")
+        if _dtype_name(d_det_rows) != "int32":
+            raise ValueError(f"DetPost.run: d_det_rows must be int32, got {d_det_rows.dtype}")
+        if not d_det_rows.is_contiguous():
+            raise ValueError("DetPost.run: d_det_rows must be contiguous")
+        for name, t in (("pred", pred), ("d_dets", d_dets), ("d_det_rows", d_det_rows)):
+            if not int(t.data_ptr()):
+                raise ValueError(f"DetPost.run: {name} has a null device address")
+        table = np.array([_geometry_row(g, s) for s, g in enumerate(geo)], dtype=np.float64)
+        return n, dtype, table, dshape[1]
+
+    def run(self, pred, geo, d_dets, d_det_rows, hip_stream: int = 0) -> None:
+        """``pred``: the detector's raw output of the first ``len(geo)`` streams, a contiguous float16 / float32 device tensor in
+        the handle's layout -- anything with ``data_ptr()``, ``dtype``, ``shape`` and ``is_contiguous()``; ``geo``: what
+        ``FrameRing.letterbox`` returned for them; ``d_dets``: (N, rows >= max_det, 6) float32, ``d_det_rows``: (N,) int32, on the
+        same device.  Asynchronous on ``hip_stream``: rows ``[x1, y1, x2, y2, conf, cls]`` in frame coordinates and their count per
+        stream; rows at and beyond the count, and streams beyond ``len(geo)``, are left alone."""
+        n, dtype, table, stride = self._check_run(pred, geo, d_dets, d_det_rows)
+        _lib.check(self._lib.boxmot_hip_detpost_run(self._handle, n, ctypes.c_void_p(int(pred.data_ptr())), dtype,
+                                                    table.ctypes.data_as(_lib.c_double_p), ctypes.c_void_p(int(d_dets.data_ptr())), stride,
+                                                    ctypes.c_void_p(int(d_det_rows.data_ptr())), ctypes.c_void_p(int(hip_stream))))
+
+    def run_host(self, pred, geo) -> list:
+        """Convenience form: ``pred`` a device tensor or a host array (uploaded); returns the rows of each stream as an (n_s, 6)
+        float32 array.  Allocates its outputs with torch and waits for the result."""
+        import torch
+        if isinstance(pred, np.ndarray):
+            pred = torch.from_numpy(np.ascontiguousarray(pred)).cuda()
+        n = len(geo)
+        d_dets = torch.empty((max(n, 1), self.max_det, 6), dtype=torch.float32, device=pred.device)
+        d_rows = torch.zeros(max(n, 1), dtype=torch.int32, device=pred.device)
+        st = torch.cuda.current_stream(pred.device)
+        self.run(pred, geo, d_dets, d_rows, hip_stream=st.cuda_stream)
+        st.synchronize()
+        rows, dets = d_rows.cpu().numpy(), d_dets.cpu().numpy()
+        return [dets[s, :rows[s]].copy() for s in range(n)]
+
+    def counters(self) -> np.ndarray:
+        """(n_streams, 3) int32 of the last run, after waiting for it: anchors that passed the threshold, candidates after the
+        top-K (``max_candidates`` when it bit), candidates NMS kept before the ``max_det`` cut."""
+        out = np.zeros((self.n_streams, 3), dtype=np.int32)
+        _lib.check(self._lib.boxmot_hip_detpost_counters(self._handle, out.ctypes.data, self.n_streams))
+        return out
+
+    def close(self) -> None:
+        h = getattr(self, "_handle", None)
+        if h:
+            self._lib.boxmot_hip_detpost_destroy(h)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

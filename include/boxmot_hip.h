@@ -374,6 +374,37 @@ typedef struct { int out_rows, out_cols, mode /*0 center, 1 topleft*/, dtype /*0
 int boxmot_hip_letterbox_geometry(int image_rows, int image_cols, const BoxMOTHipLetterbox* cfg, double* out);
 int boxmot_hip_ingest_letterbox(BoxMOTHipIngest* handle, int slot, int n_streams, const BoxMOTHipLetterbox* cfg, void* d_out, void* consumer_hip_stream);
 
+/* Detection post-processing on the device (csrc/det_post.hpp has the full definition): a detector's raw prediction tensor ->
+ * the d_dets [n_streams][out_stride_rows][6] fp32 / d_det_rows [n_streams] int32 block the *_step_device entry points read, rows
+ * [x1, y1, x2, y2, conf, cls] in frame coordinates.  No host round trip; the detector stays the caller's.
+ * d_pred: one contiguous device tensor, dtype 0 fp32 / 1 fp16; layout 0 "cn" (Ultralytics v8 / 11 raw head) (S, 4 + n_classes,
+ * n_anchors), conf = max class score; layout 1 "nc_obj" (YOLOX / YOLOv5 decoded head) (S, n_anchors, 5 + n_classes), conf = obj *
+ * max class score.  An anchor passes iff conf > conf_thres (strictly) and, with class_allow (n_classes bytes, 0 / 1; copied at
+ * create), its best class is allowed; the max_candidates (64..4096) best by (conf descending, anchor ascending), exactly; greedy
+ * NMS in that order on the letterbox-space boxes, suppression iff IoU > iou_thres (torchvision's arithmetic), between equal
+ * classes only unless agnostic -- by comparing classes, not by a coordinate offset; the first max_det survivors are written
+ * through LetterboxGeometry.to_frame's arithmetic.  Rows at and beyond d_det_rows[s] are not touched.
+ * geom: a host array [n_streams][5] = gain, top, left, rows, cols per stream (what boxmot_hip_letterbox_geometry gives, and the
+ * frame size); it is read during the call and uploaded only when it differs from the last call's.
+ * run is asynchronous on hip_stream (and ordered after the handle's previous run, whatever stream that used: the scratch is the
+ * handle's); n_streams <= the handle's, out_stride_rows >= max_det.  counters waits for the last run and copies
+ * [n_streams][3] int32: anchors that passed, candidates after the top-K, candidates kept by NMS before the max_det cut. */
+typedef struct BoxMOTHipDetPostConfig {
+    int n_streams, n_anchors, n_classes;
+    int layout;                      /* 0 cn, 1 nc_obj */
+    float conf_thres, iou_thres;     /* 0 <= conf_thres < 1 */
+    int max_candidates;              /* 64..4096 */
+    int max_det;
+    int agnostic;
+    const unsigned char* class_allow;/* n_classes entries 0 / 1, or NULL: every class */
+} BoxMOTHipDetPostConfig;
+typedef struct BoxMOTHipDetPost BoxMOTHipDetPost;
+BoxMOTHipDetPost* boxmot_hip_detpost_create(const BoxMOTHipDetPostConfig* config);
+void boxmot_hip_detpost_destroy(BoxMOTHipDetPost* handle);
+int boxmot_hip_detpost_run(BoxMOTHipDetPost* handle, int n_streams, const void* d_pred, int dtype, const double* geom, float* d_dets,
+                           int out_stride_rows, int* d_det_rows, void* hip_stream);
+int boxmot_hip_detpost_counters(BoxMOTHipDetPost* handle, int* out, int n_streams);
+
 /* ------------------------------------------------------------------------------------------------
  * DeepOCSORT (boxmot/trackers/bbox/deepocsort/deepocsort.py:235-492).  The reference has no native backend
  * for this tracker; the entry points follow the BoT-SORT ones above (same buffer, error and ownership
