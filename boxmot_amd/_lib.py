@@ -117,6 +117,12 @@ class DetPostConfig(ctypes.Structure):
                 ("agnostic", ctypes.c_int), ("class_allow", ctypes.c_void_p)]
 
 
+class DetPostObbConfig(ctypes.Structure):
+    """``BoxMOTHipDetPostObbConfig`` (include/boxmot_hip.h)."""
+
+    _fields_ = [("base", DetPostConfig), ("nms_mode", ctypes.c_int), ("regularize", ctypes.c_int)]
+
+
 class Letterbox(ctypes.Structure):
     """``BoxMOTHipLetterbox`` (include/boxmot_hip.h)."""
 
@@ -241,6 +247,7 @@ SIGNATURES = {
     "boxmot_hip_letterbox_geometry": (_I, [_I, _I, ctypes.POINTER(Letterbox), c_double_p]),
     "boxmot_hip_ingest_letterbox": (_I, [_VP, _I, _I, ctypes.POINTER(Letterbox), _VP, _VP]),
     "boxmot_hip_detpost_create": (_VP, [ctypes.POINTER(DetPostConfig)]),
+    "boxmot_hip_detpost_create_obb": (_VP, [ctypes.POINTER(DetPostObbConfig)]),
     "boxmot_hip_detpost_destroy": (None, [_VP]),
     "boxmot_hip_detpost_run": (_I, [_VP, _I, _VP, _I, c_double_p, _VP, _I, _VP, _VP]),
     "boxmot_hip_detpost_counters": (_I, [_VP, _VP, _I]),

@@ -361,6 +361,7 @@ struct BoxMOTHipIngest : DeviceBound {
 // Detection post-processing (csrc/det_post.hpp): the handle owns the per-anchor scratch, the geometry table and the counters
 struct BoxMOTHipDetPost : DeviceBound {
     BoxMOTHipDetPostConfig cfg{};
+    int obb = 0, nms_mode = 0, regularize = 0;      // an oriented handle (boxmot_hip_detpost_create_obb): 7-column rows
     uint32_t* d_keys = nullptr;                     // [n_streams][n_anchors]
     int* d_cls = nullptr;                           // [n_streams][n_anchors]
     int* d_counters = nullptr;                      // [n_streams][3]
@@ -2985,10 +2986,16 @@ int boxmot_hip_ingest_letterbox(BoxMOTHipIngest* handle, int slot, int n_streams
 }
 
 // ---- detection post-processing (csrc/det_post.hpp has the definition) ----
-BoxMOTHipDetPost* boxmot_hip_detpost_create(const BoxMOTHipDetPostConfig* c) {
+namespace {
+// both create entry points; oc: the oriented options, or null for an axis-aligned handle
+BoxMOTHipDetPost* detpost_create(const BoxMOTHipDetPostConfig* c, const BoxMOTHipDetPostObbConfig* oc) {
     BoxMOTHipDetPost* h = nullptr;
     const int ok = guard([&]() {
         if (!c) throw std::runtime_error("boxmot_hip: null detpost config");
+        if (oc && c->layout != 0)
+            throw std::runtime_error("boxmot_hip: an oriented detpost handle needs base.layout 0 (cn), got " + std::to_string(c->layout));
+        if (oc && oc->nms_mode != 0 && oc->nms_mode != 1)
+            throw std::runtime_error("boxmot_hip: unknown detpost nms_mode " + std::to_string(oc->nms_mode) + " (0 greedy, 1 fast)");
         if (c->n_streams < 1 || c->n_anchors < 1 || c->n_classes < 1)
             throw std::runtime_error("boxmot_hip: detpost needs n_streams, n_anchors and n_classes >= 1");
         if (c->layout != 0 && c->layout != 1) throw std::runtime_error("boxmot_hip: unknown detpost layout " + std::to_string(c->layout) + " (0 cn, 1 nc_obj)");
@@ -3002,6 +3009,7 @@ BoxMOTHipDetPost* boxmot_hip_detpost_create(const BoxMOTHipDetPostConfig* c) {
         h = new BoxMOTHipDetPost();
         h->cfg = *c;
         h->cfg.class_allow = nullptr;
+        if (oc) { h->obb = 1; h->nms_mode = oc->nms_mode; h->regularize = oc->regularize ? 1 : 0; }
         const size_t SA = (size_t)c->n_streams * c->n_anchors;
         void* p = nullptr;
         BM_HIP(hipMalloc(&p, SA * sizeof(uint32_t))); h->d_keys = static_cast<uint32_t*>(p);
@@ -3023,12 +3031,26 @@ BoxMOTHipDetPost* boxmot_hip_detpost_create(const BoxMOTHipDetPostConfig* c) {
         }
         BM_HIP(hipEventCreateWithFlags(&h->done, hipEventDisableTiming));
         // the workgroup's LDS grows with max_candidates and passes the 64 KB a kernel may take without saying so
-        const int lds = (int)bm::detpost_lds_bytes(c->max_candidates);
-        BM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(bm::k_detpost_select<float>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        BM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(bm::k_detpost_select<_Float16>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        if (oc) {
+            const int lds = (int)bm::detpost_obb_lds_bytes(c->max_candidates);
+            BM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(bm::k_detpost_select_obb<float>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+            BM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(bm::k_detpost_select_obb<_Float16>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        } else {
+            const int lds = (int)bm::detpost_lds_bytes(c->max_candidates);
+            BM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(bm::k_detpost_select<float>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+            BM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(bm::k_detpost_select<_Float16>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        }
     });
     if (!ok) { const std::string e = g_last_error; destroy_on(h); g_last_error = e; return nullptr; }
     return h;
+}
+}  // namespace
+
+BoxMOTHipDetPost* boxmot_hip_detpost_create(const BoxMOTHipDetPostConfig* c) { return detpost_create(c, nullptr); }
+
+BoxMOTHipDetPost* boxmot_hip_detpost_create_obb(const BoxMOTHipDetPostObbConfig* c) {
+    if (!c) { g_last_error = "boxmot_hip: null detpost config"; return nullptr; }
+    return detpost_create(&c->base, c);
 }
 
 void boxmot_hip_detpost_destroy(BoxMOTHipDetPost* handle) { destroy_on(handle); }
@@ -3070,7 +3092,8 @@ int boxmot_hip_detpost_run(BoxMOTHipDetPost* handle, int n_streams, const void* 
             if (handle->geom_valid < n_streams) handle->geom_valid = n_streams;
         }
         bm::DetPostArgs a{d_pred, handle->d_geom, handle->d_allow, handle->d_keys, handle->d_cls, d_dets, d_det_rows, handle->d_counters,
-                          c.n_anchors, c.n_classes, c.layout, c.max_candidates, c.max_det, c.agnostic ? 1 : 0, out_stride_rows, c.conf_thres, c.iou_thres};
+                          c.n_anchors, c.n_classes, c.layout, c.max_candidates, c.max_det, c.agnostic ? 1 : 0, out_stride_rows, c.conf_thres, c.iou_thres,
+                          handle->obb, handle->nms_mode, handle->regularize};
         DetPostLaunch launch{st};
         bm::detpost_launch(launch, a, n_streams, dtype);
         BM_HIP(hipGetLastError());

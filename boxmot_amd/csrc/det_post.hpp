@@ -32,6 +32,8 @@
 //    subtraction, one correctly rounded fp32 division, clip(v, lo, hi) = min(max(v, lo), hi).  d_det_rows[s] = the number of rows
 //    written; rows at and beyond it are not touched.
 // 6. Counters.  counters[s] = {anchors that passed step 1, candidates after step 2, candidates kept by NMS before the max_det cut}.
+// The oriented layout "cn_obb" (layout 0 with obb = 1: one more channel row, the angle, after the classes; 7-column rows; rotated NMS)
+// is defined at the top of det_post_obb.hpp; it shares the score kernels, stages a-c and the kernel sequence below.
 // (Parity with torchvision / Ultralytics on real detector output is not pinned by any test: tests/detpost_ref.py restates this
 // definition in NumPy, and the kernels are compared with that, bit for bit.)
 //
@@ -44,7 +46,8 @@
 //       35 us for 64 streams of 8400 x 84 fp16).  "nc_obj": a thread walks its own row; the 64 rows of a wavefront are one contiguous
 //       run of memory that the wavefront consumes completely, line by line out of the cache, but a single load instruction is
 //       strided -- there is no LDS transpose here.
-//   k_detpost_select<T>  one workgroup of DP_THREADS per stream does the rest out of dynamic LDS:
+//   k_detpost_select<T>  one workgroup of DP_THREADS per stream does the rest out of dynamic LDS (a-c are dp_select_sort, which the
+//       oriented kernel of det_post_obb.hpp shares):
 //       a. the passing count, and when more than K pass an exact radix select of the K-th largest key: four passes of an 8-bit
 //          histogram (integer LDS atomics: order-independent) over the keys that match the prefix found so far (the counting sweep
 //          fills the first pass's histogram); every sweep over the anchors loads DP_SWEEP keys per thread before it uses one;
@@ -90,19 +93,23 @@ struct DetPostArgs {
     int* counters;                  // [S][DP_COUNTERS]
     int A, nc, layout, K, max_det, agnostic, out_stride;
     float conf_thres, iou_thres;
+    int obb, nms_mode, regularize;  // the oriented layout "cn_obb" (det_post_obb.hpp): one angle row after the classes; 0 greedy / 1 fast
 };
 
 __host__ __device__ inline int detpost_slots(int K) { int p = DP_CHUNK; while (p < K) p <<= 1; return p; }
 inline size_t detpost_lds_bytes(int K) { return (size_t)detpost_slots(K) * (8 + 16 + 4 + 1) + DP_LDS_FIXED; }
+inline size_t detpost_obb_lds_bytes(int K) { return (size_t)detpost_slots(K) * (8 + 20 + 4 + 1) + DP_LDS_FIXED; }
 inline int detpost_score_grid_x(int A) { return (A + DP_SCORE_THREADS - 1) / DP_SCORE_THREADS; }
 
 __device__ inline float dp_load(const float* p, long i) { return p[i]; }
 __device__ inline float dp_load(const _Float16* p, long i) { return (float)p[i]; }
 
-// element index of channel c (0..3 box, then the layout's own columns) of anchor a of stream s
+// element index of channel c (0..3 box, then the layout's own columns) of anchor a of stream s; the channel-major layout has
+// 4 + nc channels, and one more, the angle, when oriented
 __device__ inline long dp_at(const DetPostArgs& g, int s, int a, int c) {
-    return g.layout == 0 ? ((long)s * (4 + g.nc) + c) * g.A + a : ((long)s * g.A + a) * (5 + g.nc) + c;
+    return g.layout == 0 ? ((long)s * (4 + g.nc + g.obb) + c) * g.A + a : ((long)s * g.A + a) * (5 + g.nc) + c;
 }
+__device__ inline bool dp_finite(float v) { return fabsf(v) < INFINITY; }       // false for a NaN and for +-inf
 
 template <class T>
 __global__ void __launch_bounds__(DP_SCORE_THREADS) k_detpost_score(DetPostArgs g) {
@@ -121,6 +128,7 @@ __global__ void __launch_bounds__(DP_SCORE_THREADS) k_detpost_score(DetPostArgs 
     if (g.layout == 1) conf = dp_load(pred, base - 1) * best;
     bool pass = conf > g.conf_thres;
     if (g.allow && !g.allow[cls]) pass = false;
+    if (g.obb && !dp_finite(dp_load(pred, base + g.nc * step))) pass = false;                   // the angle row follows the classes
     g.keys[(long)s * g.A + a] = pass ? __float_as_uint(conf) : 0u;
     g.cls[(long)s * g.A + a] = cls;
 }
@@ -138,7 +146,7 @@ __global__ void __launch_bounds__(DP_SCORE_VEC_THREADS) k_detpost_score_cn_vec(D
     typedef typename DpVec<T>::type V;
     const int s = (int)blockIdx.y, a0 = ((int)blockIdx.x * DP_SCORE_VEC_THREADS + (int)threadIdx.x) * N;
     if (a0 >= g.A) return;
-    const T* row = static_cast<const T*>(g.pred) + ((long)s * (4 + g.nc) + 4) * g.A + a0;
+    const T* row = static_cast<const T*>(g.pred) + ((long)s * (4 + g.nc + g.obb) + 4) * g.A + a0;
     float best[N];
     int cls[N];
 #pragma unroll
@@ -153,9 +161,17 @@ __global__ void __launch_bounds__(DP_SCORE_VEC_THREADS) k_detpost_score_cn_vec(D
         }
     }
     const long at = (long)s * g.A + a0;
+    bool finite[N];
+#pragma unroll
+    for (int u = 0; u < N; ++u) finite[u] = true;
+    if (g.obb) {
+        const V v = *reinterpret_cast<const V*>(row + (long)g.nc * g.A);
+#pragma unroll
+        for (int u = 0; u < N; ++u) finite[u] = dp_finite((float)v[u]);
+    }
 #pragma unroll
     for (int u = 0; u < N; ++u) {
-        bool pass = best[u] > g.conf_thres;
+        bool pass = best[u] > g.conf_thres && finite[u];
         if (g.allow && !g.allow[cls[u]]) pass = false;
         g.keys[at + u] = pass ? __float_as_uint(best[u]) : 0u;
         g.cls[at + u] = cls[u];
@@ -172,23 +188,42 @@ __device__ inline bool dp_suppresses(const DpBox& j, const DpBox& i, float thres
 }
 __device__ inline float dp_to_frame(float v, float off, float gain, float hi) { return fminf(fmaxf((v - off) / gain, 0.0f), hi); }
 
-template <class T>
-__global__ void __launch_bounds__(DP_THREADS) k_detpost_select(DetPostArgs g) {
-    BM_DYNAMIC_LDS_T(unsigned char, lds);
-    const int slots = detpost_slots(g.K);
-    unsigned long long* cand = reinterpret_cast<unsigned long long*>(lds);                   // [slots] key << 32 | ~anchor
-    DpBox* box = reinterpret_cast<DpBox*>(lds + (size_t)slots * 8);                          // [slots]
-    int* ccls = reinterpret_cast<int*>(lds + (size_t)slots * 24);                            // [slots]
-    int* hist = reinterpret_cast<int*>(lds + (size_t)slots * 28);                            // [256]
-    int* wsum = hist + 256;                                                                  // [16]
-    int* misc = wsum + 16;                                                                   // [8]: 0 passing, 1 prefix, 2 k_rem, 3 slot counter
-    unsigned long long* rowm = reinterpret_cast<unsigned long long*>(misc + 8);              // [64] the chunk's matrix rows
-    unsigned char* sup = lds + (size_t)slots * 28 + DP_LDS_FIXED;                            // [slots]
+// The workgroup's dynamic LDS: the candidate words, a per-candidate table of `tab_bytes` each (the box, or the oriented path's
+// Gaussian), the classes, the fixed part and the suppression flags.
+struct DpLds {
+    unsigned long long* cand;       // [slots] key << 32 | ~anchor
+    unsigned char* tab;             // [slots][tab_bytes]
+    int* ccls;                      // [slots]
+    int* hist;                      // [256]
+    int* wsum;                      // [16]
+    int* misc;                      // [8]: 0 passing, 1 prefix, 2 k_rem, 3 slot counter
+    unsigned long long* rowm;       // [64] the chunk's matrix rows
+    unsigned char* sup;             // [slots]
+};
+__device__ inline DpLds dp_lds(unsigned char* lds, int slots, int tab_bytes) {
+    DpLds m;
+    m.cand = reinterpret_cast<unsigned long long*>(lds);
+    m.tab = lds + (size_t)slots * 8;
+    m.ccls = reinterpret_cast<int*>(lds + (size_t)slots * (8 + tab_bytes));
+    m.hist = reinterpret_cast<int*>(lds + (size_t)slots * (12 + tab_bytes));
+    m.wsum = m.hist + 256;
+    m.misc = m.wsum + 16;
+    m.rowm = reinterpret_cast<unsigned long long*>(m.misc + 8);
+    m.sup = lds + (size_t)slots * (12 + tab_bytes) + DP_LDS_FIXED;
+    return m;
+}
 
-    const int s = (int)blockIdx.x, t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
+struct DpCount { int n_pass, n_cand; };
+
+// Stages a-c of the select kernels, for the whole workgroup of DP_THREADS: leaves the candidates of stream s sorted in m.cand
+// (conf descending, anchor ascending; the words beyond n_cand are 0) and m.sup cleared.  Ends with a barrier.
+__device__ inline DpCount dp_select_sort(const DetPostArgs& g, int s, const DpLds& m, int slots) {
+    unsigned long long* cand = m.cand;
+    int *hist = m.hist, *wsum = m.wsum, *misc = m.misc;
+    unsigned char* sup = m.sup;
+    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
     const int A = g.A, K = g.K;
     const uint32_t* keys = g.keys + (long)s * A;
-    const T* pred = static_cast<const T*>(g.pred);
     const unsigned long long below = (1ull << lane) - 1ull;
 
     // a. how many pass; the K-th largest key when more than K do
@@ -316,6 +351,29 @@ __global__ void __launch_bounds__(DP_THREADS) k_detpost_select(DetPostArgs g) {
         }
     }
 
+    return DpCount{n_pass, n_cand};
+}
+
+template <class T>
+__global__ void __launch_bounds__(DP_THREADS) k_detpost_select(DetPostArgs g) {
+    BM_DYNAMIC_LDS_T(unsigned char, lds);
+    const int slots = detpost_slots(g.K);
+    const DpLds m = dp_lds(lds, slots, (int)sizeof(DpBox));
+    unsigned long long* cand = m.cand;
+    DpBox* box = reinterpret_cast<DpBox*>(m.tab);
+    int* ccls = m.ccls;
+    unsigned long long* rowm = m.rowm;
+    unsigned char* sup = m.sup;
+
+    const int s = (int)blockIdx.x, t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int A = g.A;
+    const T* pred = static_cast<const T*>(g.pred);
+    const unsigned long long below = (1ull << lane) - 1ull;
+
+    // a-c. the passing count, the exact top-K, the sort
+    const DpCount cnt = dp_select_sort(g, s, m, slots);
+    const int n_pass = cnt.n_pass, n_cand = cnt.n_cand;
+
     // d. boxes
     for (int i = t; i < n_cand; i += DP_THREADS) {
         const int a = (int)(0xffffffffu - (uint32_t)cand[i]);
@@ -398,10 +456,16 @@ __global__ void __launch_bounds__(DP_THREADS) k_detpost_select(DetPostArgs g) {
     }
 }
 
+}  // namespace bm
+
+#include "det_post_obb.hpp"         // the oriented layout: k_detpost_select_obb
+
+namespace bm {
+
 // The kernel sequence of one call (L: the library's stream launcher, or the test harness's CPU-thread launcher).
 template <class L>
 inline void detpost_launch(L& launch, const DetPostArgs& g, int n_streams, int fp16, size_t* lds_bytes = nullptr) {
-    const size_t lds = detpost_lds_bytes(g.K);
+    const size_t lds = g.obb ? detpost_obb_lds_bytes(g.K) : detpost_lds_bytes(g.K);
     if (lds_bytes) *lds_bytes = lds;
     const int vec = fp16 ? DpVec<_Float16>::N : DpVec<float>::N;
     const bool wide = g.layout == 0 && g.A % vec == 0 && (uintptr_t)g.pred % 16 == 0;
@@ -409,11 +473,13 @@ inline void detpost_launch(L& launch, const DetPostArgs& g, int n_streams, int f
     if (fp16) {
         if (wide) launch(k_detpost_score_cn_vec<_Float16>, wide_grid, n_streams, DP_SCORE_VEC_THREADS, (size_t)0, g);
         else launch(k_detpost_score<_Float16>, detpost_score_grid_x(g.A), n_streams, DP_SCORE_THREADS, (size_t)0, g);
-        launch(k_detpost_select<_Float16>, n_streams, 1, DP_THREADS, lds, g);
+        if (g.obb) launch(k_detpost_select_obb<_Float16>, n_streams, 1, DP_THREADS, lds, g);
+        else launch(k_detpost_select<_Float16>, n_streams, 1, DP_THREADS, lds, g);
     } else {
         if (wide) launch(k_detpost_score_cn_vec<float>, wide_grid, n_streams, DP_SCORE_VEC_THREADS, (size_t)0, g);
         else launch(k_detpost_score<float>, detpost_score_grid_x(g.A), n_streams, DP_SCORE_THREADS, (size_t)0, g);
-        launch(k_detpost_select<float>, n_streams, 1, DP_THREADS, lds, g);
+        if (g.obb) launch(k_detpost_select_obb<float>, n_streams, 1, DP_THREADS, lds, g);
+        else launch(k_detpost_select<float>, n_streams, 1, DP_THREADS, lds, g);
     }
 }
 

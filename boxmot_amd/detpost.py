@@ -13,6 +13,12 @@ COMPARING them, not by Ultralytics' ``cls * max_wh`` coordinate offset (which ro
 conf_thres`` strictly (Ultralytics' rule, not YOLOX's ``>=``); candidates are the ``max_candidates`` best by (conf descending,
 anchor index ascending), exactly.  It is compared bit for bit with a NumPy restatement of that definition -- parity with
 torchvision or Ultralytics on real detector output is not pinned by any test.
+
+Oriented heads: ``layout="cn_obb"`` reads the Ultralytics OBB raw head (S, 4 + n_classes + 1, n_anchors) -- the angle in radians is
+the last row -- and writes 7-column rows ``[cx, cy, w, h, angle, conf, cls]``, not clipped, that ``MultiStreamBotSort(is_obb=True)``
+reads through ``step_device`` (the definition is at the top of csrc/det_post_obb.hpp).  The NMS is rotated, by the ProbIoU closed
+form in float32, ``ProbIoU >= iou`` suppresses; ``nms="greedy"`` drops a candidate that an earlier KEPT one suppresses,
+``nms="fast"`` one that ANY earlier one suppresses (what Ultralytics ``nms_rotated`` computes).
 """
 from __future__ import annotations
 
@@ -22,7 +28,8 @@ import numpy as np
 
 from boxmot_amd import _lib
 
-LAYOUTS = {"cn": 0, "nc_obj": 1}
+LAYOUTS = {"cn": 0, "nc_obj": 1, "cn_obb": 0}          # the C ABI's layout code: "cn_obb" is "cn" through boxmot_hip_detpost_create_obb
+NMS_MODES = {"greedy": 0, "fast": 1}
 _DTYPES = {"float32": 0, "float16": 1}
 
 
@@ -46,12 +53,16 @@ def _geometry_row(g, s):
 
 class DetPost:
     def __init__(self, n_streams: int, n_anchors: int, n_classes: int, layout: str = "cn", conf: float = 0.25, iou: float = 0.45,
-                 max_det: int = 256, max_candidates: int = 1024, agnostic: bool = False, classes=None):
+                 max_det: int = 256, max_candidates: int = 1024, agnostic: bool = False, classes=None, nms: str | None = None,
+                 regularize: bool | None = None):
         """``layout``: ``"cn"`` -- (S, 4 + n_classes, n_anchors), the Ultralytics v8 / 11 raw head, conf = the best class score --
-        or ``"nc_obj"`` -- (S, n_anchors, 5 + n_classes), the YOLOX / YOLOv5 decoded head, conf = obj * the best class score.
-        ``classes``: an optional allow-list of class indices, applied to an anchor's best class."""
+        ``"nc_obj"`` -- (S, n_anchors, 5 + n_classes), the YOLOX / YOLOv5 decoded head, conf = obj * the best class score -- or
+        ``"cn_obb"`` -- (S, 4 + n_classes + 1, n_anchors), the Ultralytics OBB raw head, the angle in radians as the last row.
+        ``classes``: an optional allow-list of class indices, applied to an anchor's best class.  ``nms`` (``"greedy"``, the
+        default, or ``"fast"``) and ``regularize`` (w >= h and the angle within [0, pi] in the rows; default off) belong to
+        ``"cn_obb"`` alone."""
         self._handle = None
-        self._configure(n_streams, n_anchors, n_classes, layout, conf, iou, max_det, max_candidates, agnostic, classes)
+        self._configure(n_streams, n_anchors, n_classes, layout, conf, iou, max_det, max_candidates, agnostic, classes, nms, regularize)
         self._lib = _lib.load()
         allow = None
         if self.classes is not None:
@@ -59,18 +70,28 @@ class DetPost:
             allow[self.classes] = 1
         cfg = _lib.DetPostConfig(self.n_streams, self.n_anchors, self.n_classes, LAYOUTS[self.layout], self.conf, self.iou, self.max_candidates,
                                  self.max_det, int(self.agnostic), None if allow is None else allow.ctypes.data)
-        self._handle = self._lib.boxmot_hip_detpost_create(ctypes.byref(cfg))          # (the table is copied by the call)
+        if self.is_obb:
+            ocfg = _lib.DetPostObbConfig(cfg, NMS_MODES[self.nms], int(self.regularize))
+            self._handle = self._lib.boxmot_hip_detpost_create_obb(ctypes.byref(ocfg))
+        else:
+            self._handle = self._lib.boxmot_hip_detpost_create(ctypes.byref(cfg))      # (the table is copied by the call)
         if not self._handle:
             raise RuntimeError(_lib.last_error())
 
     def _configure(self, n_streams, n_anchors, n_classes, layout="cn", conf=0.25, iou=0.45, max_det=256, max_candidates=1024, agnostic=False,
-                   classes=None):
+                   classes=None, nms=None, regularize=None):
         """the options, checked; touches neither the library nor a device"""
         for name, v in (("n_streams", n_streams), ("n_anchors", n_anchors), ("n_classes", n_classes), ("max_det", max_det)):
             if int(v) != v or int(v) < 1:
                 raise ValueError(f"DetPost: {name} must be an integer >= 1, got {v!r}")
         if layout not in LAYOUTS:
-            raise ValueError(f"DetPost: unknown layout {layout!r} (\"cn\" or \"nc_obj\")")
+            raise ValueError(f"DetPost: unknown layout {layout!r} (\"cn\", \"nc_obj\" or \"cn_obb\")")
+        is_obb = layout == "cn_obb"
+        if not is_obb and (nms is not None or regularize is not None):
+            raise ValueError(f"DetPost: nms= and regularize= belong to layout \"cn_obb\", not to {layout!r}")
+        nms = "greedy" if nms is None else nms
+        if nms not in NMS_MODES:
+            raise ValueError(f"DetPost: unknown nms {nms!r} (\"greedy\" or \"fast\")")
         if not 0.0 <= float(conf) < 1.0:
             raise ValueError(f"DetPost: conf must be within [0, 1), got {conf!r}")
         if not 0.0 <= float(iou) <= 1.0:
@@ -85,10 +106,13 @@ class DetPost:
         self.n_streams, self.n_anchors, self.n_classes, self.layout = int(n_streams), int(n_anchors), int(n_classes), layout
         self.conf, self.iou = float(np.float32(conf)), float(np.float32(iou))          # the thresholds are float32 on the device
         self.max_det, self.max_candidates, self.agnostic, self.classes = int(max_det), int(max_candidates), bool(agnostic), classes
+        self.is_obb, self.nms, self.regularize = is_obb, nms if is_obb else None, bool(regularize) if is_obb else None
+        self.n_channels = 5 + self.n_classes if is_obb or layout == "nc_obj" else 4 + self.n_classes       # per anchor, in the layout
+        self.det_cols = 7 if is_obb else 6
 
     def pred_shape(self, n: int | None = None) -> tuple:
         n = self.n_streams if n is None else n
-        return (n, 4 + self.n_classes, self.n_anchors) if self.layout == "cn" else (n, self.n_anchors, 5 + self.n_classes)
+        return (n, self.n_anchors, self.n_channels) if self.layout == "nc_obj" else (n, self.n_channels, self.n_anchors)
 
     def _check_run(self, pred, geo, d_dets, d_det_rows):
         """(n_streams, dtype code, geometry table) of a call; raises ValueError naming what is wrong"""
@@ -104,8 +128,8 @@ class DetPost:
         if not pred.is_contiguous():
             raise ValueError("DetPost.run: pred must be contiguous")
         dshape = tuple(int(v) for v in d_dets.shape)
-        if len(dshape) != 3 or dshape[0] < n or dshape[2] != 6:
-            raise ValueError(f"DetPost.run: d_dets must have shape (N >= {n}, rows, 6), got {dshape}")
+        if len(dshape) != 3 or dshape[0] < n or dshape[2] != self.det_cols:
+            raise ValueError(f"DetPost.run: d_dets must have shape (N >= {n}, rows, {self.det_cols}), got {dshape}")
         if dshape[1] < self.max_det:
             raise ValueError(f"DetPost.run: d_dets holds {dshape[1]} rows per stream, fewer than max_det = {self.max_det}")
         if _dtype_name(d_dets) != "float32":
@@ -130,7 +154,8 @@ class DetPost:
         the handle's layout -- anything with ``data_ptr()``, ``dtype``, ``shape`` and ``is_contiguous()``; ``geo``: what
         ``FrameRing.letterbox`` returned for them; ``d_dets``: (N, rows >= max_det, 6) float32, ``d_det_rows``: (N,) int32, on the
         same device.  Asynchronous on ``hip_stream``: rows ``[x1, y1, x2, y2, conf, cls]`` in frame coordinates and their count per
-        stream; rows at and beyond the count, and streams beyond ``len(geo)``, are left alone."""
+        stream; rows at and beyond the count, and streams beyond ``len(geo)``, are left alone.  Layout ``"cn_obb"``: ``d_dets`` is
+        (N, rows >= max_det, 7), rows ``[cx, cy, w, h, angle, conf, cls]``, not clipped to the frame."""
         n, dtype, table, stride = self._check_run(pred, geo, d_dets, d_det_rows)
         _lib.check(self._lib.boxmot_hip_detpost_run(self._handle, n, ctypes.c_void_p(int(pred.data_ptr())), dtype,
                                                     table.ctypes.data_as(_lib.c_double_p), ctypes.c_void_p(int(d_dets.data_ptr())), stride,
@@ -138,12 +163,12 @@ class DetPost:
 
     def run_host(self, pred, geo) -> list:
         """Convenience form: ``pred`` a device tensor or a host array (uploaded); returns the rows of each stream as an (n_s, 6)
-        float32 array.  Allocates its outputs with torch and waits for the result."""
+        float32 array, (n_s, 7) for layout ``"cn_obb"``.  Allocates its outputs with torch and waits for the result."""
         import torch
         if isinstance(pred, np.ndarray):
             pred = torch.from_numpy(np.ascontiguousarray(pred)).cuda()
         n = len(geo)
-        d_dets = torch.empty((max(n, 1), self.max_det, 6), dtype=torch.float32, device=pred.device)
+        d_dets = torch.empty((max(n, 1), self.max_det, self.det_cols), dtype=torch.float32, device=pred.device)
         d_rows = torch.zeros(max(n, 1), dtype=torch.int32, device=pred.device)
         st = torch.cuda.current_stream(pred.device)
         self.run(pred, geo, d_dets, d_rows, hip_stream=st.cuda_stream)

@@ -405,6 +405,22 @@ int boxmot_hip_detpost_run(BoxMOTHipDetPost* handle, int n_streams, const void* 
                            int out_stride_rows, int* d_det_rows, void* hip_stream);
 int boxmot_hip_detpost_counters(BoxMOTHipDetPost* handle, int* out, int n_streams);
 
+/* Oriented detector heads (csrc/det_post_obb.hpp has the full definition): layout "cn_obb", the Ultralytics OBB raw head
+ * (S, 4 + n_classes + 1, n_anchors) -- box rows cx, cy, w, h, the class rows, and the angle in radians as the LAST row.  base is
+ * read as above with base.layout == 0; an anchor must also have a finite angle to pass.  NMS is rotated, by the ProbIoU closed form
+ * in fp32 on the letterbox-space boxes, suppression iff ProbIoU >= iou_thres (Ultralytics nms_rotated's rule, not the `>` above);
+ * nms_mode 0 greedy: a candidate is dropped iff an earlier KEPT one suppresses it; 1 fast: iff ANY earlier one does (what
+ * nms_rotated computes).  The handle is run, read and destroyed with boxmot_hip_detpost_run / _counters / _destroy; on such a
+ * handle d_dets is [n_streams][out_stride_rows][7], rows [cx, cy, w, h, angle, conf, cls] in frame coordinates, NOT clipped to
+ * the frame -- what an is_obb tracker handle's step_device reads.  regularize != 0: the emitted rows have w >= h and the angle
+ * within [0, pi]. */
+typedef struct BoxMOTHipDetPostObbConfig {
+    BoxMOTHipDetPostConfig base;     /* base.layout must be 0 */
+    int nms_mode;                    /* 0 greedy, 1 fast */
+    int regularize;
+} BoxMOTHipDetPostObbConfig;
+BoxMOTHipDetPost* boxmot_hip_detpost_create_obb(const BoxMOTHipDetPostObbConfig* config);
+
 /* ------------------------------------------------------------------------------------------------
  * DeepOCSORT (boxmot/trackers/bbox/deepocsort/deepocsort.py:235-492).  The reference has no native backend
  * for this tracker; the entry points follow the BoT-SORT ones above (same buffer, error and ownership

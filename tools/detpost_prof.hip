@@ -2,12 +2,14 @@
 // through its own kernel sequence detpost_launch) for S streams of one prediction tensor, beside the first half of what they
 // replace: the device-to-host copy of the S-stream tensor (into pinned and into pageable memory).  The other half, the NumPy
 // reference on the host, is timed by detpost_prof.py on the same tensor.  Every launch has its own pair of HIP events.  Prints one
-// line per kernel -- median, min and max in microseconds -- and a checksum of stream 0's output (the sum of its rows' 6 columns, and
-// its counters) that detpost_prof.py compares with the reference's.
+// line per kernel -- median, min and max in microseconds -- and a checksum of stream 0's output (the sum of its rows' 6 columns, 7
+// on the oriented path, and its counters) that detpost_prof.py compares with the reference's.
 //
 //     hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -o detpost_prof tools/detpost_prof.hip
 //     ./detpost_prof pred.bin [streams = 16] [anchors = 8400] [classes = 80] [layout = 0] [fp16 = 1] [K = 1024] [max_det = 256] [repeats = 30]
-// pred.bin: ONE stream's tensor, (4 + nc, A) or (A, 5 + nc), raw; every stream gets a copy.  conf 0.25, iou 0.45, class-aware,
+//                   [obb = 0] [nms_mode = 0]
+// pred.bin: ONE stream's tensor, (4 + nc, A) or (A, 5 + nc), raw; every stream gets a copy.  obb = 1: the oriented layout
+// (det_post_obb.hpp), (4 + nc + 1, A) with layout 0, nms_mode 0 greedy / 1 fast; the host copies are not timed again.  conf 0.25, iou 0.45, class-aware,
 // geometry of a 1080 x 1920 frame in a centred 640 x 640 letterbox.
 #include <hip/hip_runtime.h>
 
@@ -42,12 +44,13 @@ struct TimedLaunch {            // every kernel of the sequence between its own 
 int main(int argc, char** argv) {
     auto arg = [&](int k, int d) { return argc > k ? std::atoi(argv[k]) : d; };
     if (argc < 2) { std::fprintf(stderr, "usage: detpost_prof pred.bin [streams anchors classes layout fp16 K max_det repeats]\n"); return 1; }
-    const int S = arg(2, 16), A = arg(3, 8400), nc = arg(4, 80), layout = arg(5, 0), fp16 = arg(6, 1), K = arg(7, 1024), max_det = arg(8, 256), reps = arg(9, 30);
-    if (S < 1 || A < 1 || nc < 1 || (layout != 0 && layout != 1) || K < bm::DP_K_MIN || K > bm::DP_K_MAX || max_det < 1 || reps < 20) {
+    const int S = arg(2, 16), A = arg(3, 8400), nc = arg(4, 80), layout = arg(5, 0), fp16 = arg(6, 1), K = arg(7, 1024), max_det = arg(8, 256), reps = arg(9, 30),
+              obb = arg(10, 0), mode = arg(11, 0), cols = obb ? 7 : 6;
+    if (S < 1 || A < 1 || nc < 1 || (layout != 0 && layout != 1) || (obb != 0 && obb != 1) || (obb && layout != 0) || (mode != 0 && mode != 1) || K < bm::DP_K_MIN || K > bm::DP_K_MAX || max_det < 1 || reps < 20) {
         std::fprintf(stderr, "streams, anchors, classes >= 1, layout 0 or 1, K within 64..4096, repeats >= 20\n");
         return 1;
     }
-    const size_t per = (size_t)A * ((layout == 0 ? 4 : 5) + nc) * (fp16 ? 2 : 4), bytes = per * S;
+    const size_t per = (size_t)A * ((layout == 0 ? 4 + obb : 5) + nc) * (fp16 ? 2 : 4), bytes = per * S;
     std::vector<unsigned char> one(per);
     {
         FILE* f = std::fopen(argv[1], "rb");
@@ -64,20 +67,25 @@ int main(int argc, char** argv) {
     CHECK(hipMalloc(&d_cls, (size_t)S * A * 4));
     CHECK(hipMalloc(&d_rows, (size_t)S * 4));
     CHECK(hipMalloc(&d_counters, (size_t)S * bm::DP_COUNTERS * 4));
-    CHECK(hipMalloc(&d_dets, (size_t)S * max_det * 6 * 4));
+    CHECK(hipMalloc(&d_dets, (size_t)S * max_det * cols * 4));
     CHECK(hipMalloc(&d_geom, (size_t)S * sizeof(bm::DetPostGeom)));
     CHECK(hipHostMalloc(&h_pinned, bytes, hipHostMallocDefault));
     std::vector<unsigned char> h_pageable(bytes);
     for (int s = 0; s < S; ++s) CHECK(hipMemcpy((unsigned char*)d_pred + per * s, one.data(), per, hipMemcpyHostToDevice));
     std::vector<bm::DetPostGeom> geom(S, bm::DetPostGeom{(float)(1.0 / 3.0), 140.f, 0.f, 1080.f, 1920.f});
     CHECK(hipMemcpy(d_geom, geom.data(), S * sizeof(bm::DetPostGeom), hipMemcpyHostToDevice));
-    CHECK(hipMemset(d_dets, 0, (size_t)S * max_det * 6 * 4));
-    const int lds = (int)bm::detpost_lds_bytes(K);
-    CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(bm::k_detpost_select<float>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(bm::k_detpost_select<_Float16>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    CHECK(hipMemset(d_dets, 0, (size_t)S * max_det * cols * 4));
+    const int lds = (int)(obb ? bm::detpost_obb_lds_bytes(K) : bm::detpost_lds_bytes(K));
+    if (obb) {
+        CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(bm::k_detpost_select_obb<float>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(bm::k_detpost_select_obb<_Float16>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    } else {
+        CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(bm::k_detpost_select<float>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(bm::k_detpost_select<_Float16>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    }
     hipStream_t st;
     CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    const bm::DetPostArgs a{d_pred, d_geom, nullptr, d_keys, d_cls, d_dets, d_rows, d_counters, A, nc, layout, K, max_det, 0, max_det, 0.25f, 0.45f};
+    const bm::DetPostArgs a{d_pred, d_geom, nullptr, d_keys, d_cls, d_dets, d_rows, d_counters, A, nc, layout, K, max_det, 0, max_det, 0.25f, 0.45f, obb, mode, 0};
     std::vector<hipEvent_t> ev(8 * (size_t)reps);
     for (auto& e : ev) CHECK(hipEventCreate(&e));
     for (int k = 0; k < 5; ++k) { TimedLaunch warm{st, ev.data()}; bm::detpost_launch(warm, a, S, fp16); }
@@ -87,6 +95,7 @@ int main(int argc, char** argv) {
         hipEvent_t* e = &ev[8 * (size_t)k];
         TimedLaunch tl{st, e};
         bm::detpost_launch(tl, a, S, fp16);
+        if (obb) { CHECK(hipStreamSynchronize(st)); continue; }
         CHECK(hipEventRecord(e[4], st)); CHECK(hipMemcpyAsync(h_pinned, d_pred, bytes, hipMemcpyDeviceToHost, st)); CHECK(hipEventRecord(e[5], st));
         CHECK(hipStreamSynchronize(st));
         CHECK(hipEventRecord(e[6], st)); CHECK(hipMemcpyAsync(h_pageable.data(), d_pred, bytes, hipMemcpyDeviceToHost, st)); CHECK(hipEventRecord(e[7], st));
@@ -99,23 +108,26 @@ int main(int argc, char** argv) {
         CHECK(hipEventElapsedTime(&t_score[k], e[0], e[1]));
         CHECK(hipEventElapsedTime(&t_select[k], e[2], e[3]));
         CHECK(hipEventElapsedTime(&t_both[k], e[0], e[3]));
+        if (obb) continue;
         CHECK(hipEventElapsedTime(&t_pin[k], e[4], e[5]));
         CHECK(hipEventElapsedTime(&t_page[k], e[6], e[7]));
     }
-    std::vector<float> rows((size_t)max_det * 6);
+    std::vector<float> rows((size_t)max_det * cols);
     int n = 0, counters[bm::DP_COUNTERS];
     CHECK(hipMemcpy(&n, d_rows, 4, hipMemcpyDeviceToHost));
     CHECK(hipMemcpy(counters, d_counters, sizeof(counters), hipMemcpyDeviceToHost));
     CHECK(hipMemcpy(rows.data(), d_dets, rows.size() * 4, hipMemcpyDeviceToHost));
     double sum = 0.0;
-    for (int k = 0; k < n * 6; ++k) sum += rows[k];
-    std::printf("%d streams of %d anchors x %d classes, layout %d, %s, K %d, max_det %d: tensor %.2f MB, LDS %d bytes per workgroup\n", S, A, nc, layout,
-                fp16 ? "fp16" : "fp32", K, max_det, bytes * 1e-6, lds);
+    for (int k = 0; k < n * cols; ++k) sum += rows[k];
+    std::printf("%d streams of %d anchors x %d classes, layout %d%s, %s, K %d, max_det %d: tensor %.2f MB, LDS %d bytes per workgroup\n", S, A, nc, layout,
+                obb ? (mode ? " oriented, fast NMS" : " oriented, greedy NMS") : "", fp16 ? "fp16" : "fp32", K, max_det, bytes * 1e-6, lds);
     report("k_detpost_score", t_score);
-    report("k_detpost_select", t_select);
+    report(obb ? "k_detpost_select_obb" : "k_detpost_select", t_select);
     report("both kernels", t_both);
-    report("D2H of pred, pinned", t_pin);
-    report("D2H of pred, pageable", t_page);
+    if (!obb) {
+        report("D2H of pred, pinned", t_pin);
+        report("D2H of pred, pageable", t_page);
+    }
     std::printf("checksum: rows %d counters %d %d %d sum %.6f\n", n, counters[0], counters[1], counters[2], sum);
     return 0;
 }

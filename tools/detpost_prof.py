@@ -7,7 +7,12 @@ reference's rows, and times that reference on this host: the host path is the co
 
     python tools/detpost_prof.py [--streams 1 16 64] [--rates 0.01 0.3] [--repeats 30] [--out DIR]
 
-Needs a gfx950 device.  profiles/detpost_timing.txt is the output of one such run."""
+``--obb`` times the ORIENTED layout instead (csrc/det_post_obb.hpp): A = 21 504 anchors (a 1024 x 1024 input), 15 classes, fp16, 64
+streams, a sparse and a busy scene; per scene the axis-aligned path on the same boxes (the tensor without its angle row) and the
+oriented path in both NMS modes, from the same run.  The checksums are compared with tests/detpost_obb_ref.py; where a scene has a
+pair within the reference's margin of the threshold the NMS decisions may differ, which is reported and not an error.
+
+Needs a gfx950 device.  profiles/detpost_timing.txt and profiles/detpost_obb_timing.txt are the outputs of one such run each."""
 import argparse
 import os
 import subprocess
@@ -22,7 +27,7 @@ ROOT = Path(__file__).resolve().parent.parent
 SRC = ROOT / "tools" / "detpost_prof.hip"
 EXE = ROOT / "tools" / "_build" / "detpost_prof"
 CSRC = ROOT / "boxmot_amd" / "csrc"
-DEPS = [SRC, CSRC / "det_post.hpp", CSRC / "kernel_macros.hpp"]
+DEPS = [SRC, CSRC / "det_post.hpp", CSRC / "det_post_obb.hpp", CSRC / "kernel_macros.hpp"]
 sys.path[:0] = [str(ROOT / "tests"), str(ROOT)]          # the reference lives with the tests
 
 
@@ -33,6 +38,75 @@ def build() -> Path:
     return EXE
 
 
+def obb_scene(A, nc, rate, seed, n_obj=150, size=1024):
+    """One stream's (4 + nc + 1, A) fp16 tensor: clustered oriented boxes (sides 8..160 px, aspect <= 8) around n_obj objects, confs
+    quantised to 1 / 128, an anchor 'active' with probability ``rate``"""
+    rng = np.random.default_rng(seed)
+    short = rng.integers(8, 41, n_obj)
+    long_ = np.minimum(160, short * rng.integers(1, 9, n_obj))
+    flip = rng.random(n_obj) < 0.5
+    obj = np.stack([rng.integers(60, size - 60, n_obj), rng.integers(60, size - 60, n_obj), np.where(flip, short, long_), np.where(flip, long_, short)], 1)
+    obj_ang = rng.integers(-50, 51, n_obj) / 32.0
+    which = rng.integers(0, n_obj, A)
+    box = (obj[which] + rng.integers(-24, 25, (A, 4)) / 4.0).astype(np.float32)
+    ang = (obj_ang[which] + rng.integers(-8, 9, A) / 128.0).astype(np.float32)
+    cf = rng.integers(128 // 3, 129, A).astype(np.float32) / np.float32(128)
+    cf = np.where(rng.random(A) < rate, cf, cf * np.float32(0.125)).astype(np.float32)
+    cls = (which + (rng.random(A) < 0.2)) % nc
+    sc = cf[:, None] * (rng.integers(0, 5, (A, nc)).astype(np.float32) / np.float32(8))
+    sc[np.arange(A), cls] = cf
+    return np.concatenate([box.T, sc.T, ang[None]], 0).astype(np.float16)
+
+
+def run_exe(exe, args, want, lenient=False):
+    """the measuring program's output, printed; 0, or the exit status to stop with"""
+    r = subprocess.run([str(exe), *[str(v) for v in args]], capture_output=True, text=True, timeout=300)
+    print(r.stdout, end="", flush=True)
+    if r.returncode != 0:
+        print(r.stderr, file=sys.stderr)
+        return r.returncode or 1
+    got = [ln for ln in r.stdout.splitlines() if ln.startswith("checksum:")][0]
+    if got == want:
+        print("checksum equals the reference's", flush=True)
+    elif lenient:
+        print(f"checksum differs from the reference's (`{want}`): this scene has pairs within the margin of the threshold", flush=True)
+    else:
+        print(f"CHECKSUM MISMATCH: device `{got}`, reference `{want}`", file=sys.stderr)
+        return 1
+    return 0
+
+
+def checksum(rows, counters):
+    return f"checksum: rows {len(rows)} counters {counters[0]} {counters[1]} {counters[2]} sum {float(rows.astype(np.float64).sum()):.6f}"
+
+
+def main_obb(exe, a, out) -> int:
+    import detpost_obb_ref as oref
+    import detpost_ref as ref
+    A, nc, K, max_det, S = 21504, 15, 1024, 256, 64
+    geo = ref.GEO_CENTER
+    for name, rate in (("sparse", 0.01), ("busy", 0.3)):
+        pred = obb_scene(A, nc, rate, 1)
+        path, path_aa = out / f"detpost_obb_pred_{name}.bin", out / f"detpost_aa_pred_{name}.bin"
+        pred.tofile(path)
+        np.ascontiguousarray(pred[:4 + nc]).tofile(path_aa)
+        rows, counters = ref.detpost(pred[:4 + nc], geo, "cn", 0.25, 0.45, max_det, K)
+        print(f"== {name} scene (pass rate {rate}): {counters[0]} of {A} anchors pass, {counters[1]} candidates", flush=True)
+        print(f"-- axis-aligned, the same boxes without the angle row: {counters[2]} kept by NMS", flush=True)
+        status = run_exe(exe, [path_aa, S, A, nc, 0, 1, K, max_det, a.repeats], checksum(rows, counters))
+        if status:
+            return status
+        found = oref.pairs(pred, 0.25, 0.45, K)
+        print(f"-- oriented: the reference's margin to the threshold {found.margin:.2e}, float32 against float64 {found.err32:.2e}", flush=True)
+        for mode, word in enumerate(oref.NMS_MODES):
+            rows, counters = oref.detpost_obb(pred, geo, 0.25, 0.45, max_det, K, nms_mode=word, found=found)
+            print(f"-- oriented, {word}: {counters[2]} kept by NMS", flush=True)
+            status = run_exe(exe, [path, S, A, nc, 0, 1, K, max_det, a.repeats, 1, mode], checksum(rows, counters), lenient=found.margin < oref.MARGIN)
+            if status:
+                return status
+    return 0
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--streams", type=int, nargs="+", default=[1, 16, 64])
@@ -40,10 +114,15 @@ def main() -> int:
     ap.add_argument("--repeats", type=int, default=30)
     ap.add_argument("--out", default=None, help="directory for the tensor files (default: a temporary one)")
     ap.add_argument("--build-only", action="store_true", help="compile the measuring program and stop (no device needed)")
+    ap.add_argument("--obb", action="store_true", help="the oriented layout beside the axis-aligned one at 64 x 21504 x 15 (see above)")
     a = ap.parse_args()
     exe = build()
     if a.build_only:
         return 0
+    if a.obb:
+        out = Path(a.out) if a.out else Path(tempfile.mkdtemp())
+        out.mkdir(parents=True, exist_ok=True)
+        return main_obb(exe, a, out)
     import detpost_ref as ref
     A, nc, K, max_det = 8400, 80, 1024, 256
     geo = ref.GEO_CENTER
@@ -62,17 +141,9 @@ def main() -> int:
         print(f"== pass rate {rate}: {counters[0]} of {A} anchors pass, {counters[1]} candidates, {counters[2]} kept by NMS, {len(rows)} rows", flush=True)
         print(f"NumPy reference of ONE stream on this host (tests/detpost_ref.py): median {1e3 * sorted(times)[2]:.2f} ms of 5", flush=True)
         for S in a.streams:
-            r = subprocess.run([str(exe), str(path), str(S), str(A), str(nc), "0", "1", str(K), str(max_det), str(a.repeats)], capture_output=True, text=True,
-                               timeout=300)
-            print(r.stdout, end="", flush=True)
-            if r.returncode != 0:
-                print(r.stderr, file=sys.stderr)
-                return r.returncode
-            got = [ln for ln in r.stdout.splitlines() if ln.startswith("checksum:")][0]
-            if got != want:
-                print(f"CHECKSUM MISMATCH: device `{got}`, reference `{want}`", file=sys.stderr)
-                return 1
-            print("checksum equals the reference's", flush=True)
+            status = run_exe(exe, [path, S, A, nc, 0, 1, K, max_det, a.repeats], want)
+            if status:
+                return status
     return 0
 
 
