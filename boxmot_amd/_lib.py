@@ -213,6 +213,8 @@ SIGNATURES = {
     "boxmot_hip_reid_set_preprocess": (_I, [_VP, ctypes.c_char_p]),
     "boxmot_hip_reid_compute_features": (_I, [_VP, _VP, _I, _I, _I, _VP, _I, _I, _VP, _I]),
     "boxmot_hip_reid_preprocess": (_I, [_VP, _VP, _I, _I, _I, _VP, _I, _I, _VP]),
+    "boxmot_hip_reid_debug_crop_planes": (_I, [_VP, _VP, _I, _I, _I, _VP, _I, _I, _VP, _VP]),
+    "boxmot_hip_reid_debug_obb_geometry": (_I, [_VP, _VP, _I, _I, _VP]),
     "boxmot_hip_reid_compute_features_batch": (_I, [_VP, _VP, _VP, _VP, _I, _VP, _VP, _I, _I, _VP, _I]),
     "boxmot_hip_reid_preprocess_batch": (_I, [_VP, _VP, _VP, _VP, _I, _VP, _VP, _I, _I, _VP]),
     "boxmot_hip_reid_last_time_ms": (_I, [_VP, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),

@@ -20,6 +20,7 @@
 #include "deepocsort_step.hpp"
 #include "strongsort_step.hpp"
 #include "reid_engine.hpp"
+#include "crop_list.hpp"
 #include "cmc_ecc.hpp"
 #include "cmc_sof.hpp"
 #include "ingest_nv12.hpp"
@@ -181,37 +182,6 @@ __global__ void __launch_bounds__(NTHR) strongsort_step_kernel(bm::SsStepArgs ar
     bm::ss_step_stream<NTHR>(args, args.stream_base + blockIdx.x, s_int, s_dbl, dyn_lds);
 }
 
-// Build the ReID crop list on the device: every detection with conf > track_high_thresh
-// (botsort.py:191-192, :260).  One workgroup per stream; ranges reserved with one atomic.
-__global__ void build_crop_list_kernel(const float* dets, const int* n_dets, int max_dets, double high,
-                                       int* crop_count, int* crop_stream, float* crop_boxes, int* crop_row,
-                                       int stream_base, int inclusive = 0) {
-    __shared__ int s_base;
-    __shared__ int s_cnt;
-    const int s = stream_base + blockIdx.x;
-    const int n = n_dets[s];
-    if (threadIdx.x == 0) s_cnt = 0;
-    __syncthreads();
-    const float* d = dets + (long)s * max_dets * bm::DET_COLS;
-    int mine = 0;
-    auto pass = [&](int j) { const double cf = (double)d[j * bm::DET_COLS + 4]; return inclusive ? cf >= high : cf > high; };
-    for (int j = threadIdx.x; j < n; j += blockDim.x)
-        if (pass(j)) ++mine;
-    const int local = atomicAdd(&s_cnt, mine);
-    __syncthreads();
-    if (threadIdx.x == 0) s_base = atomicAdd(crop_count, s_cnt);
-    __syncthreads();
-    int k = s_base + local;
-    for (int j = threadIdx.x; j < n; j += blockDim.x) {
-        if (pass(j)) {
-            crop_stream[k] = s;
-            crop_row[k] = s * max_dets + j;
-            for (int q = 0; q < 4; ++q) crop_boxes[k * 4 + q] = d[j * bm::DET_COLS + q];
-            ++k;
-        }
-    }
-}
-
 // A backbone family that sizes its launches on the host (the wide OSNets, CLIP-ReID) and a caller that declared an upper bound on the
 // step's crops (set_crop_bound): the list is filled up to the bound with copies of its first entry -- the same crop computes the same
 // embedding and writes it to the same row -- so the launches are sized by the bound and the count never travels to the host.  A
@@ -219,8 +189,9 @@ __global__ void build_crop_list_kernel(const float* dets, const int* n_dets, int
 // `ndets_out` (the detection counts the frame step of this call reads) = the caller's counts, or -1 for EVERY stream when the count
 // exceeds the bound: the step kernels treat a negative count as "stream not stepped in this call", so a frame whose crops did not all
 // get an embedding changes no tracker state and returns no rows (round-4 advisor finding: it used to step with stale embeddings).
+// `crop_geo` (oriented handles, else null): the geometry rows [..][8] are padded the same way.
 __global__ void pad_crop_list_kernel(const int* crop_count, int bound, int* crop_stream, float* crop_boxes, int* crop_row, int* flag,
-                                     const int* ndets_in, int* ndets_out, int n_streams) {
+                                     const int* ndets_in, int* ndets_out, int n_streams, double* crop_geo = nullptr) {
     const int n = *crop_count;
     if (blockIdx.x == 0)
         for (int s = threadIdx.x; s < n_streams; s += blockDim.x) ndets_out[s] = n > bound ? -1 : ndets_in[s];
@@ -228,9 +199,15 @@ __global__ void pad_crop_list_kernel(const int* crop_count, int bound, int* crop
     const int s0 = n > 0 ? crop_stream[0] : 0, r0 = n > 0 ? crop_row[0] : 0;
     float b0[4];
     for (int q = 0; q < 4; ++q) b0[q] = n > 0 ? crop_boxes[q] : 0.0f;
+    double g0[8];
+    if (crop_geo) {
+        if (n > 0) for (int q = 0; q < 8; ++q) g0[q] = crop_geo[q];
+        else { const float nan_box[5] = {NAN, 0.f, 0.f, 0.f, 0.f}; bm::obb_crop_geometry(nan_box, g0); }      // no crops at all: blank ones
+    }
     for (int i = n + blockIdx.x * blockDim.x + threadIdx.x; i < bound; i += gridDim.x * blockDim.x) {
         crop_stream[i] = s0; crop_row[i] = r0;
         for (int q = 0; q < 4; ++q) crop_boxes[i * 4 + q] = b0[q];
+        if (crop_geo) for (int q = 0; q < 8; ++q) crop_geo[(long)i * 8 + q] = g0[q];
     }
 }
 
@@ -420,6 +397,9 @@ struct HandleCore : DeviceBound {
     const uint8_t** d_frames = nullptr;
     std::unique_ptr<bm::ReidEngine> reid;
     int* d_crop_count = nullptr; int* d_crop_stream = nullptr; float* d_crop_boxes = nullptr; int* d_crop_row = nullptr;
+    // [S * max_dets][8] crop geometry (obb_crop_geometry.hpp) of an oriented handle with in-handle ReID, made by the oriented
+    // crop-list kernel; null on every other handle -- its presence is what makes a ReID pass an oriented one
+    double* d_crop_geo = nullptr;
     // growth of the tables: what the tracker's allocate function handed out, in order; slots in use per stream after the last
     // host update (-1 = unknown: a device-resident step ran since)
     std::vector<std::pair<void*, size_t>> table_rec;
@@ -728,10 +708,15 @@ void core_upload_frame(HandleCore* h, int s, const uint8_t* image, int rows, int
 
 // the per-stream (or per-image) size table is handed to a ReID engine for one pass only
 struct FrameDimsScope { bm::ReidEngine* e; ~FrameDimsScope() { if (e) e->set_frame_dims(nullptr); } };
+// ... and so is the crop geometry of an oriented handle: a later axis-aligned user of the engine never sees it
+struct CropGeoScope { bm::ReidEngine* e; ~CropGeoScope() { if (e) e->set_obb_geometry(nullptr); } };
+static_assert(bm::OBB_CROP_DET_COLS == bm::obb::DET_COLS && bm::OBB_CROP_CONF_COL == bm::obb::CONF_COL,
+              "the oriented crop-list kernel reads the oriented handle's detection rows");
 
 // The crop list of streams [s0, s0 + n) -- every detection passing the confidence test (`conf > thresh`, or `>=` when inclusive)
 // -- and the ReID pass over it on stream `st`, embeddings into the rows of `d_embs` (rows of skipped detections keep stale values;
 // the step kernels never read them).  rows / cols: the one frame size (replaced by the declared sizes where there are any).
+// On an oriented handle (d_crop_geo) the list carries the crops' geometry instead of boxes and the engine samples through it.
 // Where the backbone sizes its launches on the host: by `bound` when the caller declared one (>= 0; `nd_step` then receives the
 // detection counts the frame step is to read, see pad_crop_list_kernel, and `*bounded` is raised as soon as that kernel is
 // queued; returns true), else by the count read back.
@@ -744,7 +729,13 @@ bool core_reid_pass(HandleCore* h, hipStream_t st, int s0, int n, const float* d
         h->reid->set_frame_dims(h->fs_mixed ? h->d_fs_dims : nullptr);
     }
     BM_HIP(hipMemsetAsync(h->d_crop_count, 0, 4, st));
-    hipLaunchKernelGGL(build_crop_list_kernel, dim3(n), dim3(256), 0, st, d_dets, d_ndets, h->nd, thresh,
+    CropGeoScope geo_scope{h->d_crop_geo ? h->reid.get() : nullptr};
+    if (h->d_crop_geo) {
+        hipLaunchKernelGGL(bm::build_crop_list_obb_kernel, dim3(n), dim3(256), 0, st, d_dets, d_ndets, h->nd, thresh,
+                           h->d_crop_count, h->d_crop_stream, h->d_crop_row, h->d_crop_geo, s0, inclusive);
+        h->reid->set_obb_geometry(h->d_crop_geo);
+    } else
+    hipLaunchKernelGGL(bm::build_crop_list_kernel, dim3(n), dim3(256), 0, st, d_dets, d_ndets, h->nd, thresh,
                        h->d_crop_count, h->d_crop_stream, h->d_crop_boxes, h->d_crop_row, s0, inclusive);
     if (h->reid->counted_ok()) {
         // crop count stays on the device: launches cover the capacity, surplus workgroups exit at once
@@ -756,7 +747,7 @@ bool core_reid_pass(HandleCore* h, hipStream_t st, int s0, int n, const float* d
         const int m = bound < n * h->nd ? bound : n * h->nd;
         // (a bound of 0 -- "no crops in this step" -- is checked like any other: one workgroup compares the count with it)
         hipLaunchKernelGGL(pad_crop_list_kernel, dim3(m > 0 ? (m + 255) / 256 : 1), dim3(256), 0, st, (const int*)h->d_crop_count, m,
-                           h->d_crop_stream, h->d_crop_boxes, h->d_crop_row, h->d_crop_count + 1, d_ndets, nd_step, n);
+                           h->d_crop_stream, h->d_crop_boxes, h->d_crop_row, h->d_crop_count + 1, d_ndets, nd_step, n, h->d_crop_geo);
         if (bounded) *bounded = true;
         if (m > 0) h->reid->run(d_frames, h->d_crop_stream, h->d_crop_boxes, 4, m, cols, rows, d_embs, h->d_crop_row, st);
         return true;
@@ -825,6 +816,8 @@ void alloc_det_io(BoxMOTHipBotSort* h) {
     core_alloc_sized(h, h->nd, (size_t)h->S * h->nd);
     release(h->owned, h->d_cmc_boxes);
     h->d_cmc_boxes = h->is_obb ? zalloc<float>((size_t)h->S * h->nd * 4, h->owned) : nullptr;
+    release(h->owned, h->d_crop_geo);
+    h->d_crop_geo = (h->is_obb && h->cfg.with_reid) ? zalloc<double>((size_t)h->S * h->nd * 8, h->owned) : nullptr;
 }
 
 std::unique_ptr<bm::ReidEngine> new_reid_engine(BoxMOTHipBotSort* h, int nd) {
@@ -914,7 +907,9 @@ void build(BoxMOTHipBotSort* h) {
         // the oriented tracks (STrack.multi_gmc_obb, botsort_track.py:197-230: kf_warp_wave of the oriented layout); the in-handle
         // estimators mask by axis-aligned detection boxes and are not wired to oriented tables (the reference estimates on the
         // enclosing boxes, botsort.py:147-158: the caller does that and supplies the warp).  Embeddings of oriented detections come
-        // from the caller (the reference crops rotated rectangles with cv2.warpAffine, reid/backends/base_backend.py:92-118).
+        // from the caller or from the handle's own ReID pass over the rotated rectangles (the reference's cv2.warpAffine crops,
+        // reid/backends/base_backend.py:92-118: build_crop_list_obb_kernel + the k_crop_resize_obb* kernels); its weights arrive through
+        // boxmot_hip_botsort_set_reid_blob -- a reid_model_path at creation is still refused, below.
         // (cmc_method ecc / sof run on an oriented handle too: SOF is masked by the enclosing boxes, obb_enclosing_boxes_kernel)
         if ((c.reid_model_path && c.reid_model_path[0]) || !h->reid_path.empty())      // (create() moves the path into the handle)
             throw std::runtime_error("boxmot_hip: an oriented-box handle takes embeddings from the caller (embs), not from in-handle ReID weights");
@@ -1211,8 +1206,6 @@ void host_update(BoxMOTHipBotSort* h, int s0, int n, const StreamIn* in, int det
             throw std::runtime_error("boxmot_hip: embedding width does not match emb_dim");
         if (h->cfg.with_reid && in[k].embs == nullptr && rows > 0) need_reid = true;
     }
-    if (need_reid && h->is_obb)
-        throw std::runtime_error("boxmot_hip: an oriented-box handle with with_reid = 1 needs the embeddings of the frame's detections (embs)");
     if (need_reid)
         for (int k = 0; k < n; ++k)
             if (in[k].embs != nullptr && in[k].det_rows > 0)
@@ -2013,7 +2006,6 @@ int boxmot_hip_botsort_step_device(BoxMOTHipBotSort* handle, const float* d_dets
         const float* embs = d_embs;
         bool reid_here = false;
         if (handle->cfg.with_reid && d_embs == nullptr) {
-            if (handle->is_obb) throw std::runtime_error("boxmot_hip: an oriented-box handle with with_reid = 1 needs d_embs");
             if (!d_frames) throw std::runtime_error("boxmot_hip: with_reid needs d_embs or d_frames");
             // pipeline stage 1: this frame's ReID on `reid_stream`, into the table the step before last has finished reading
             hipStream_t rs = core_pipe_begin_reid(handle);
@@ -2282,27 +2274,9 @@ static bool reid_host_boxes(const float* boxes, int n, int box_cols, std::vector
     if (obb) {
         // _crop_obb (base_backend.py:91-117): getRotationMatrix2D about the box centre, shifted so that the centre lands on the middle
         // of the (round(w), round(h)) output; cv2.warpAffine inverts the matrix in double precision before it samples
+        // (obb_crop_geometry.hpp: the one function the device's crop-list kernel uses too; a non-finite box is a blank crop)
         geo.resize((size_t)n * 8);
-        const float rad2deg = 180.0f / 3.14159265358979323846f;         // np.degrees on a float32 scalar
-        for (int i = 0; i < n; ++i) {
-            const float* bx = boxes + (size_t)i * box_cols;
-            const double cx = bx[0], cy = bx[1];
-            const double bw = bx[2] > 1.0f ? (double)bx[2] : 1.0, bh = bx[3] > 1.0f ? (double)bx[3] : 1.0;
-            const int ow = std::max((int)std::nearbyint(bw), 1), oh = std::max((int)std::nearbyint(bh), 1);
-            const double a = (double)(bx[4] * rad2deg) * (3.14159265358979323846 / 180.0);
-            const double alpha = std::cos(a), beta = std::sin(a);
-            double m00 = alpha, m01 = beta, m02 = (1 - alpha) * cx - beta * cy, m10 = -beta, m11 = alpha, m12 = beta * cx + (1 - alpha) * cy;
-            m02 += ow / 2.0 - cx;
-            m12 += oh / 2.0 - cy;
-            double D = m00 * m11 - m01 * m10;
-            D = D != 0 ? 1.0 / D : 0.0;
-            const double A11 = m11 * D, A22 = m00 * D;
-            double* g = geo.data() + (size_t)i * 8;
-            g[0] = ow; g[1] = oh;
-            g[2] = A11; g[3] = m01 * (-D); g[5] = m10 * (-D); g[6] = A22;
-            g[4] = -g[2] * m02 - g[3] * m12;
-            g[7] = -g[5] * m02 - g[6] * m12;
-        }
+        for (int i = 0; i < n; ++i) bm::obb_crop_geometry(boxes + (size_t)i * box_cols, geo.data() + (size_t)i * 8);
     } else {
         for (int i = 0; i < n; ++i)
             for (int q = 0; q < 4; ++q) b[i * 4 + q] = boxes[(size_t)i * box_cols + q];
@@ -2494,6 +2468,45 @@ int boxmot_hip_reid_preprocess(BoxMOTHipReID* handle, const uint8_t* image, int 
                                         image_rows, handle->stream);
         BM_HIP(hipMemcpyAsync(out_crops, handle->engine->crops_buffer(),
                               (size_t)n_boxes * bm::REID_IN_H * bm::REID_IN_W * 3 * 4, hipMemcpyDeviceToHost, handle->stream));
+        BM_HIP(hipStreamSynchronize(handle->stream));
+    });
+}
+
+// Debug read-back of what the fp32-grade family (mode 2) takes as its input: the (hi, lo) fp16 RGBX planes [n][262][136][4] of the
+// boxes' crops, border included, as raw halves.
+int boxmot_hip_reid_debug_crop_planes(BoxMOTHipReID* handle, const uint8_t* image, int image_rows, int image_cols, int image_channels,
+                                      const float* boxes, int n_boxes, int box_cols, uint16_t* out_hi, uint16_t* out_lo) {
+    return guard_on(handle, [&]() {
+        ObbScope scope{handle};
+        reid_stage(handle, image, image_rows, image_cols, image_channels, boxes, n_boxes, box_cols);
+        const _Float16 *hi = nullptr, *lo = nullptr;
+        if (!handle->engine->hp_crop_planes(hi, lo)) throw std::runtime_error("boxmot_hip: the (hi, lo) crop planes exist in ReID mode 2 only");
+        if (n_boxes == 0) return;
+        if (!out_hi || !out_lo) throw std::runtime_error("boxmot_hip: null argument");
+        handle->engine->preprocess(handle->d_frames, handle->d_crop_stream, handle->d_boxes, 4, n_boxes, image_cols, image_rows, handle->stream);
+        const size_t bytes = (size_t)n_boxes * bm::STEM_ROWS * bm::STEM_COLS * 4 * 2;
+        BM_HIP(hipMemcpyAsync(out_hi, hi, bytes, hipMemcpyDeviceToHost, handle->stream));
+        BM_HIP(hipMemcpyAsync(out_lo, lo, bytes, hipMemcpyDeviceToHost, handle->stream));
+        BM_HIP(hipStreamSynchronize(handle->stream));
+    });
+}
+
+// Debug: the crop geometry of n oriented boxes [cx, cy, w, h, angle, ...] as the DEVICE computes it (obb_geometry_kernel; the
+// crop-list kernel of an oriented tracker handle calls the same function) -> out_geo [n][8] doubles.
+int boxmot_hip_reid_debug_obb_geometry(BoxMOTHipReID* handle, const float* boxes, int n_boxes, int box_cols, double* out_geo) {
+    return guard_on(handle, [&]() {
+        if (!handle) throw std::runtime_error("boxmot_hip: null ReID handle");
+        if (n_boxes < 0 || box_cols < 5) throw std::runtime_error("boxmot_hip: oriented boxes have at least 5 columns");
+        if (n_boxes == 0) return;
+        if (!boxes || !out_geo) throw std::runtime_error("boxmot_hip: null argument");
+        std::vector<void*> tmp;
+        struct Free { std::vector<void*>& v; ~Free() { for (void* p : v) (void)hipFree(p); } } free_tmp{tmp};
+        float* d_b = dev_alloc<float>((size_t)n_boxes * box_cols, tmp);
+        double* d_g = dev_alloc<double>((size_t)n_boxes * 8, tmp);
+        BM_HIP(hipMemcpyAsync(d_b, boxes, (size_t)n_boxes * box_cols * 4, hipMemcpyHostToDevice, handle->stream));
+        hipLaunchKernelGGL(bm::obb_geometry_kernel, dim3((n_boxes + 63) / 64), dim3(64), 0, handle->stream, (const float*)d_b, box_cols, n_boxes, d_g);
+        BM_HIP(hipGetLastError());
+        BM_HIP(hipMemcpyAsync(out_geo, d_g, (size_t)n_boxes * 64, hipMemcpyDeviceToHost, handle->stream));
         BM_HIP(hipStreamSynchronize(handle->stream));
     });
 }

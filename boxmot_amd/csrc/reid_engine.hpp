@@ -166,6 +166,14 @@ public:
     int preprocess_mode() const { return pad_; }
     const OsnetLayout& layout() const { return L_; }
     float* crops_buffer() { return crops_; }
+    // mode 2: the (hi, lo) fp16 RGBX planes [n][262][136][4] that preprocess() fills (debug read-back); false in the other modes
+    bool hp_crop_planes(const _Float16*& hi, const _Float16*& lo) const {
+        if (mode_ != 2) return false;
+        const bool whp = !fused_ready_ && wide_hp_;
+        hi = whp ? wide_hp_->crops_h() : crops_h_;
+        lo = whp ? wide_hp_->crops_l() : crops_l_;
+        return hi && lo;
+    }
 
     // crops only (normalised NHWC fp32) for `n` boxes
     void preprocess(const uint8_t* const* d_frames, const int* d_crop_stream, const float* d_boxes,
@@ -175,7 +183,17 @@ public:
             const bool whp = !fused_ready_ && wide_hp_;
             if (n > (whp ? wide_hp_->max_crops() : fused_cap_)) throw std::runtime_error("ReID: crop batch exceeds the engine capacity");
             if (n == 0) return;
-            if (obb_geo_) throw std::runtime_error("ReID mode 2 (fused fp32-grade kernels): oriented-box crops run in modes 0 / 1");
+            if (obb_geo_) {     // oriented boxes: the same planes, sampled through the boxes' geometry (k_crop_resize_obb_rgbx_hl)
+                _Float16 *oh = whp ? wide_hp_->crops_h() : crops_h_, *ol = whp ? wide_hp_->crops_l() : crops_l_;
+                const int* cnt = whp ? static_cast<const int*>(nullptr) : d_count_;
+                if (dims_)
+                    hipLaunchKernelGGL(k_crop_resize_obb_rgbx_hl_sized, dim3(n, REID_IN_H / 16), dim3(REID_IN_W), 0, st, d_frames, d_crop_stream,
+                                       obb_geo_, dims_, d_lut_, oh, ol, 16, cnt, pad_);
+                else
+                    hipLaunchKernelGGL(k_crop_resize_obb_rgbx_hl, dim3(n, REID_IN_H / 16), dim3(REID_IN_W), 0, st, d_frames, d_crop_stream,
+                                       obb_geo_, W, H, d_lut_, oh, ol, 16, cnt, pad_);
+                return;
+            }
             if (dims_)
                 hipLaunchKernelGGL(k_crop_resize_rgbx_hl_sized, dim3(n, REID_IN_H / 16), dim3(REID_IN_W), 0, st, d_frames, d_crop_stream, d_boxes,
                                    box_stride, dims_, d_lut_, whp ? wide_hp_->crops_h() : crops_h_, whp ? wide_hp_->crops_l() : crops_l_, 16,
@@ -193,15 +211,16 @@ public:
         const int rows_per_block = 16;
         if (obb_geo_) {         // oriented boxes: the rectified crop is sampled on demand (k_crop_resize_obb), same output layouts
             const dim3 grid(n, REID_IN_H / rows_per_block), block(REID_IN_W);
+            const int* no_count = nullptr;      // (only the fused x0.25 planes are ever filled by a counted run)
             if (dims_) {
-                if (wide) hipLaunchKernelGGL((k_crop_resize_obb_sized<_Float16, true>), grid, block, 0, st, d_frames, d_crop_stream, obb_geo_, dims_, d_lut_, wide_->crops_buffer(), rows_per_block, pad_);
-                else if (fused) hipLaunchKernelGGL((k_crop_resize_obb_sized<_Float16, true>), grid, block, 0, st, d_frames, d_crop_stream, obb_geo_, dims_, d_lut_, crops_h_, rows_per_block, pad_);
-                else hipLaunchKernelGGL((k_crop_resize_obb_sized<float, false>), grid, block, 0, st, d_frames, d_crop_stream, obb_geo_, dims_, d_lut_, crops_, rows_per_block, pad_);
+                if (wide) hipLaunchKernelGGL((k_crop_resize_obb_sized<_Float16, true>), grid, block, 0, st, d_frames, d_crop_stream, obb_geo_, dims_, d_lut_, wide_->crops_buffer(), rows_per_block, pad_, no_count);
+                else if (fused) hipLaunchKernelGGL((k_crop_resize_obb_sized<_Float16, true>), grid, block, 0, st, d_frames, d_crop_stream, obb_geo_, dims_, d_lut_, crops_h_, rows_per_block, pad_, d_count_);
+                else hipLaunchKernelGGL((k_crop_resize_obb_sized<float, false>), grid, block, 0, st, d_frames, d_crop_stream, obb_geo_, dims_, d_lut_, crops_, rows_per_block, pad_, no_count);
                 return;
             }
-            if (wide) hipLaunchKernelGGL((k_crop_resize_obb<_Float16, true>), grid, block, 0, st, d_frames, d_crop_stream, obb_geo_, W, H, d_lut_, wide_->crops_buffer(), rows_per_block, pad_);
-            else if (fused) hipLaunchKernelGGL((k_crop_resize_obb<_Float16, true>), grid, block, 0, st, d_frames, d_crop_stream, obb_geo_, W, H, d_lut_, crops_h_, rows_per_block, pad_);
-            else hipLaunchKernelGGL((k_crop_resize_obb<float, false>), grid, block, 0, st, d_frames, d_crop_stream, obb_geo_, W, H, d_lut_, crops_, rows_per_block, pad_);
+            if (wide) hipLaunchKernelGGL((k_crop_resize_obb<_Float16, true>), grid, block, 0, st, d_frames, d_crop_stream, obb_geo_, W, H, d_lut_, wide_->crops_buffer(), rows_per_block, pad_, no_count);
+            else if (fused) hipLaunchKernelGGL((k_crop_resize_obb<_Float16, true>), grid, block, 0, st, d_frames, d_crop_stream, obb_geo_, W, H, d_lut_, crops_h_, rows_per_block, pad_, d_count_);
+            else hipLaunchKernelGGL((k_crop_resize_obb<float, false>), grid, block, 0, st, d_frames, d_crop_stream, obb_geo_, W, H, d_lut_, crops_, rows_per_block, pad_, no_count);
             return;
         }
         if (dims_) {
@@ -278,7 +297,7 @@ public:
         if (n_max == 0) return;
         d_count_ = d_count;
         BM_HIP(hipEventRecord(ev_[0], st));
-        const bool fuse_stem = fuse_stem_ && !pad_;
+        const bool fuse_stem = fuse_stem_ && !pad_ && !obb_geo_;        // (the fused stems sample axis-aligned rectangles only)
         if (!fuse_stem) preprocess(d_frames, d_crop_stream, d_boxes, box_stride, n_max, W, H, st);
         BM_HIP(hipEventRecord(ev_[1], st));
         hipEvent_t a = take_event(), b = take_event();

@@ -1537,4 +1537,37 @@ __global__ void k_crop_resize_rgbx_hl_sized(const uint8_t* const* frames, const 
     crop_resize_rgbx_hl_body(frames, crop_stream, boxes, box_stride, d.W, d.H, lut, out_hi, out_lo, rows_per_block, pad);
 }
 
+// The same planes for oriented boxes: sampled like k_crop_resize_obb (reid_kernels_v1.hpp: crop_resize_obb_rows -- obb_pixel under the
+// ordinary resize / resize_pad, geo = [out_w, out_h, inverse 2x3 map] per crop), written like crop_resize_rgbx_hl_body.  A gather
+// with double-precision address arithmetic: nothing here for the matrix pipe or LDS.
+__device__ __forceinline__ void crop_resize_obb_rgbx_hl_body(const uint8_t* const* frames, const int* crop_stream, const double* geo, int W,
+                                                             int H, const float* lut, _Float16* out_hi, _Float16* out_lo,
+                                                             int rows_per_block, int pad) {
+    crop_resize_obb_rows(frames, crop_stream, geo, W, H, rows_per_block, pad, [=](int i, int dy, int dx, const int* v) {
+        h4 ph, pl;
+        for (int c = 0; c < 3; ++c) {
+            const float f = lut[c * 256 + v[c]];
+            ph[c] = (_Float16)f;
+            pl[c] = (_Float16)(f - (float)ph[c]);
+        }
+        ph[3] = (_Float16)0.f; pl[3] = (_Float16)0.f;
+        const long o = (((long)i * STEM_ROWS + dy + 3) * STEM_COLS + dx + 3) * 4;
+        *reinterpret_cast<h4*>(out_hi + o) = ph;
+        *reinterpret_cast<h4*>(out_lo + o) = pl;
+    });
+}
+__global__ void k_crop_resize_obb_rgbx_hl(const uint8_t* const* frames, const int* crop_stream, const double* geo, int W, int H,
+                                          const float* lut, _Float16* out_hi, _Float16* out_lo, int rows_per_block, const int* count,
+                                          int pad) {
+    if (count && (int)blockIdx.x >= *count) return;
+    crop_resize_obb_rgbx_hl_body(frames, crop_stream, geo, W, H, lut, out_hi, out_lo, rows_per_block, pad);
+}
+__global__ void k_crop_resize_obb_rgbx_hl_sized(const uint8_t* const* frames, const int* crop_stream, const double* geo, const int* dims,
+                                                const float* lut, _Float16* out_hi, _Float16* out_lo, int rows_per_block,
+                                                const int* count, int pad) {
+    if (count && (int)blockIdx.x >= *count) return;
+    const FrameDims d = frame_dims_of(dims, crop_stream, blockIdx.x);
+    crop_resize_obb_rgbx_hl_body(frames, crop_stream, geo, d.W, d.H, lut, out_hi, out_lo, rows_per_block, pad);
+}
+
 }  // namespace bm

@@ -132,7 +132,7 @@ __device__ inline int preprocess_sample_f(const Fetch& px, const CropRect& r, co
 // ---------------------------------------------------------------------------
 // Oriented boxes: BaseModelBackend._crop_obb (base_backend.py:91-117) = cv2.getRotationMatrix2D + cv2.warpAffine(INTER_LINEAR,
 // BORDER_CONSTANT 0).  The rectified crop is never materialised: pixel (y, x) of it is computed on demand from the frame with
-// warpAffine's arithmetic -- inverse 2x3 map `im` (inverted on the host in double precision, boxmot_hip.hip), fixed-point sampling
+// warpAffine's arithmetic -- inverse 2x3 map `im` (inverted in double precision, on the host or the device: obb_crop_geometry.hpp), fixed-point sampling
 // position on the 1/32-pixel grid, integer bilinear weights (32 - fx)(32 - fy) * 32 ... summing to 2^15, taps outside the frame = 0
 // -- and the ordinary resize / resize_pad runs on top of it.  geo = [out_w, out_h, im0 .. im5] (8 doubles per box).
 // ---------------------------------------------------------------------------
@@ -163,9 +163,11 @@ __device__ __forceinline__ FrameDims frame_dims_of(const int* dims, const int* c
     return FrameDims{BM_UNIFORM_I32(dims[2 * s]), BM_UNIFORM_I32(dims[2 * s + 1])};
 }
 
-template <typename T, bool RGBX>
-__device__ __forceinline__ void crop_resize_obb_body(const uint8_t* const* frames, const int* crop_stream, const double* geo, int W, int H,
-                                                     const float* lut, T* out, int rows_per_block, int pad) {
+// The rows of one workgroup of an oriented crop: store(i, dy, dx, v) receives the three resized uint8 samples of output pixel
+// (dy, dx) of crop i in RGB order.  Shared by every output layout (the fp32 / fp16 tensors below, the (hi, lo) planes of reid_hp.hpp).
+template <class Store>
+__device__ __forceinline__ void crop_resize_obb_rows(const uint8_t* const* frames, const int* crop_stream, const double* geo, int W, int H,
+                                                     int rows_per_block, int pad, const Store& store) {
     const int i = blockIdx.x;
     const int dx = threadIdx.x;               // 0..127
     const uint8_t* frame = frames[crop_stream[i]];
@@ -178,29 +180,40 @@ __device__ __forceinline__ void crop_resize_obb_body(const uint8_t* const* frame
     const PadGeom g = pad_geom(r, REID_IN_W, REID_IN_H);
     const int y0 = blockIdx.y * rows_per_block;
     for (int dy = y0; dy < y0 + rows_per_block && dy < REID_IN_H; ++dy) {
-        T v3[3];
-        for (int c = 0; c < 3; ++c) {         // c = RGB output channel; source is BGR
-            const int v = preprocess_sample_f(px, r, g, pad, ax, dy, dx, 2 - c, REID_IN_W, REID_IN_H);
-            v3[c] = (T)lut[c * 256 + v];
-        }
-        if constexpr (RGBX) {
-            T* o = out + (((long)i * 262 + dy + 3) * 136 + dx + 3) * 4;
-            o[0] = v3[0]; o[1] = v3[1]; o[2] = v3[2]; o[3] = (T)0.f;
-        } else {
-            T* o = out + (((long)i * REID_IN_H + dy) * REID_IN_W + dx) * 3;
-            o[0] = v3[0]; o[1] = v3[1]; o[2] = v3[2];
-        }
+        int v[3];
+        for (int c = 0; c < 3; ++c)           // c = RGB output channel; source is BGR
+            v[c] = preprocess_sample_f(px, r, g, pad, ax, dy, dx, 2 - c, REID_IN_W, REID_IN_H);
+        store(i, dy, dx, v);
     }
 }
 
 template <typename T, bool RGBX>
+__device__ __forceinline__ void crop_resize_obb_body(const uint8_t* const* frames, const int* crop_stream, const double* geo, int W, int H,
+                                                     const float* lut, T* out, int rows_per_block, int pad) {
+    crop_resize_obb_rows(frames, crop_stream, geo, W, H, rows_per_block, pad, [=](int i, int dy, int dx, const int* v) {
+        const T v0 = (T)lut[v[0]], v1 = (T)lut[256 + v[1]], v2 = (T)lut[512 + v[2]];
+        if constexpr (RGBX) {
+            T* o = out + (((long)i * 262 + dy + 3) * 136 + dx + 3) * 4;
+            o[0] = v0; o[1] = v1; o[2] = v2; o[3] = (T)0.f;
+        } else {
+            T* o = out + (((long)i * REID_IN_H + dy) * REID_IN_W + dx) * 3;
+            o[0] = v0; o[1] = v1; o[2] = v2;
+        }
+    });
+}
+
+// `count` (may be null: no count): the number of crops on the device; a counted run launches the capacity and the surplus
+// workgroups leave before they read a geometry row nobody wrote
+template <typename T, bool RGBX>
 __global__ void k_crop_resize_obb(const uint8_t* const* frames, const int* crop_stream, const double* geo, int W, int H, const float* lut,
-                                  T* out, int rows_per_block, int pad) {
+                                  T* out, int rows_per_block, int pad, const int* count = nullptr) {
+    if (count && (int)blockIdx.x >= *count) return;
     crop_resize_obb_body<T, RGBX>(frames, crop_stream, geo, W, H, lut, out, rows_per_block, pad);
 }
 template <typename T, bool RGBX>
 __global__ void k_crop_resize_obb_sized(const uint8_t* const* frames, const int* crop_stream, const double* geo, const int* dims,
-                                        const float* lut, T* out, int rows_per_block, int pad) {
+                                        const float* lut, T* out, int rows_per_block, int pad, const int* count = nullptr) {
+    if (count && (int)blockIdx.x >= *count) return;
     const FrameDims d = frame_dims_of(dims, crop_stream, blockIdx.x);
     crop_resize_obb_body<T, RGBX>(frames, crop_stream, geo, d.W, d.H, lut, out, rows_per_block, pad);
 }

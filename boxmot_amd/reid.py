@@ -93,6 +93,28 @@ class HipReID:
                 self._handle, a.ctypes.data, a.shape[0], a.shape[1], 3, boxes.ctypes.data, n, boxes.shape[1], out.ctypes.data))
         return np.ascontiguousarray(np.transpose(out, (0, 3, 1, 2)))
 
+    def debug_crop_planes(self, xyxys, img):
+        """Debug (mode 2 only): the (hi, lo) float16 RGBX planes the fp32-grade family takes as input, ``(N, 262, 136, 4)`` each
+        with the 3-pixel zero border; ``hi.astype(float32) + lo.astype(float32)`` is the normalised crop to fp32 grade."""
+        boxes = self._boxes(xyxys)
+        n = len(boxes)
+        if n > self.max_crops:
+            raise ValueError("more boxes than max_crops")
+        a = self._image(img)
+        hi = np.zeros((n, 262, 136, 4), dtype=np.float16)
+        lo = np.zeros((n, 262, 136, 4), dtype=np.float16)
+        _lib.check(self._lib.boxmot_hip_reid_debug_crop_planes(
+            self._handle, a.ctypes.data, a.shape[0], a.shape[1], 3, boxes.ctypes.data, n, boxes.shape[1], hi.ctypes.data, lo.ctypes.data))
+        return hi, lo
+
+    def debug_obb_geometry(self, boxes) -> np.ndarray:
+        """Debug: ``(N, 8)`` float64 crop geometry (out_w, out_h, inverse 2x3 map) of oriented boxes ``[cx, cy, w, h, angle]`` as the
+        device computes it for the crop list of an oriented tracker handle (``oracle.crops.obb_crop_geometry`` is the definition)."""
+        b = np.ascontiguousarray(np.asarray(boxes, dtype=np.float32).reshape(-1, 5))
+        out = np.zeros((len(b), 8), dtype=np.float64)
+        _lib.check(self._lib.boxmot_hip_reid_debug_obb_geometry(self._handle, b.ctypes.data, len(b), 5, out.ctypes.data))
+        return out
+
     def _batch(self, boxes_list, imgs):
         """Validated inputs of a batch call, before anything reaches the library: (images, per-image box counts, the boxes of all
         images stacked, image index of every box).  ``ValueError`` names the image at fault."""

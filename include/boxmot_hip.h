@@ -75,7 +75,9 @@ typedef struct BoxMOTHipBotSortConfig {
                                       * 1 = oriented detections [cx cy w h angle conf cls] -> rows [cx cy w h angle id conf cls det_ind]
                                       * (basetracker.py:179-201 decides this from the first frame's column count; botsort.py:120-131,
                                       * bytetrack.py:283-291, KalmanFilterXYWH(ndim=5), iou_batch_obb): the 10-state filter and the
-                                      * rotated-rectangle IoU run in the frame step; cmc_method must be none, embeddings come as embs */
+                                      * rotated-rectangle IoU run in the frame step; embeddings come as embs or from the handle's own
+                                      * ReID pass over the rotated rectangles (weights through boxmot_hip_botsort_set_reid_blob;
+                                      * reid_model_path is refused on an oriented handle) */
 } BoxMOTHipBotSortConfig;
 
 typedef struct BoxMOTHipBotSort BoxMOTHipBotSort;
@@ -156,10 +158,14 @@ int boxmot_hip_botsort_update_batch_frames(
     float* const* out_tracks, int out_capacity_rows, int* out_rows);
 
 /* Device-resident step for all streams (asynchronous on the handle's stream):
- *   d_dets   [n_streams][max_dets][6] fp32, d_det_rows [n_streams] int32,
+ *   d_dets   [n_streams][max_dets][6] fp32 ([7] on an oriented handle), d_det_rows [n_streams] int32,
  *   d_embs   [n_streams][max_dets][emb_dim] fp32 or NULL (NULL + with_reid -> ReID runs on d_frames),
  *   d_frames device array of n_streams device pointers to (rows, cols, 3) uint8 BGR frames, or NULL,
- *   d_out    [n_streams][max_dets][8] fp32, d_out_rows [n_streams] int32.
+ *   d_out    [n_streams][max_dets][8] fp32 ([9] on an oriented handle), d_out_rows [n_streams] int32.
+ * Axis-aligned and oriented (is_obb) handles alike: with d_embs == NULL the handle builds the crop list of the detections above
+ * track_high_thresh on the device -- for oriented rows with the crop geometry of _crop_obb, computed there too -- and embeds the crops
+ * of d_frames with its ReID engine (every set_reid_mode; per-stream frame sizes honoured) before the frame step reads them.  Neither
+ * d_embs nor d_frames, or no ReID weights, is an error.
  * Call boxmot_hip_botsort_synchronize() before reading the outputs. */
 int boxmot_hip_botsort_step_device(
     BoxMOTHipBotSort* handle,
@@ -186,7 +192,7 @@ int boxmot_hip_botsort_status(BoxMOTHipBotSort* handle, int* out_status, int cap
 
 /* ReID weights from memory (same blob format as reid_model_path). */
 int boxmot_hip_botsort_set_reid_blob(BoxMOTHipBotSort* handle, const float* blob, long n_floats);
-/* precision / kernel family of the ReID engine: 0 = per-layer fp32 kernels, 1 = fused fp16 MFMA kernels */
+/* precision / kernel family of the ReID engine: 0 = per-layer fp32 kernels, 1 = fused fp16 MFMA kernels, 2 = fused fp32-grade kernels */
 int boxmot_hip_botsort_set_reid_mode(BoxMOTHipBotSort* handle, int mode);
 
 /* boxmot_botsort_last_reid_*_time_ms, c_api.hpp:57-60 (device time of the last update, HIP events) */
@@ -245,6 +251,15 @@ int boxmot_hip_reid_compute_features(
 int boxmot_hip_reid_preprocess(
     BoxMOTHipReID* handle, const uint8_t* image, int image_rows, int image_cols, int image_channels,
     const float* boxes, int n_boxes, int box_cols, float* out_crops);
+/* Debug: the input of the fp32-grade family (mode 2 only) for these boxes -- the (hi, lo) fp16 RGBX planes, (n, 262, 136, 4) raw
+   halves each, 3-pixel zero border and zero X channel included; hi + lo is the normalised crop to fp32 grade */
+int boxmot_hip_reid_debug_crop_planes(
+    BoxMOTHipReID* handle, const uint8_t* image, int image_rows, int image_cols, int image_channels,
+    const float* boxes, int n_boxes, int box_cols, uint16_t* out_hi, uint16_t* out_lo);
+/* Debug: the crop geometry of oriented boxes (n, box_cols >= 5) [cx, cy, w, h, angle, ...] as the device computes it for the crop list
+   of an oriented tracker handle: out_geo (n, 8) fp64 = out_w, out_h, inverse 2x3 map.  A box with a non-finite field gets the
+   geometry of a blank crop: 1, 1, [0 0 -1e6; 0 0 -1e6]. */
+int boxmot_hip_reid_debug_obb_geometry(BoxMOTHipReID* handle, const float* boxes, int n_boxes, int box_cols, double* out_geo);
 /* Boxes of many images in one device pass: images[k] is (image_rows[k], image_cols[k], 3) uint8 BGR -- the sizes may differ --,
    box_image[i] is the image that box i lies in, boxes as for compute_features (all rows of one call have box_cols columns).
    out (n_boxes, feature_dim) in the order of the boxes; more than max_crops boxes run in passes of max_crops.  Every crop is what
