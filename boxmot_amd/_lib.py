@@ -123,6 +123,12 @@ class DetPostObbConfig(ctypes.Structure):
     _fields_ = [("base", DetPostConfig), ("nms_mode", ctypes.c_int), ("regularize", ctypes.c_int)]
 
 
+class DetPostTiledConfig(ctypes.Structure):
+    """``BoxMOTHipDetPostTiledConfig`` (include/boxmot_hip.h)."""
+
+    _fields_ = [("base", DetPostConfig), ("n_tiles", ctypes.c_int), ("merge", ctypes.c_int)]
+
+
 class Letterbox(ctypes.Structure):
     """``BoxMOTHipLetterbox`` (include/boxmot_hip.h)."""
 
@@ -253,6 +259,10 @@ SIGNATURES = {
     "boxmot_hip_detpost_destroy": (None, [_VP]),
     "boxmot_hip_detpost_run": (_I, [_VP, _I, _VP, _I, c_double_p, _VP, _I, _VP, _VP]),
     "boxmot_hip_detpost_counters": (_I, [_VP, _VP, _I]),
+    "boxmot_hip_letterbox_tile_geometry": (_I, [_I, _I, _VP, ctypes.POINTER(Letterbox), c_double_p]),
+    "boxmot_hip_ingest_letterbox_tiles": (_I, [_VP, _I, _I, _I, _VP, ctypes.POINTER(Letterbox), _VP, _VP]),
+    "boxmot_hip_detpost_create_tiled": (_VP, [ctypes.POINTER(DetPostTiledConfig)]),
+    "boxmot_hip_detpost_run_tiled": (_I, [_VP, _I, _VP, _I, c_double_p, _VP, _I, _VP, _VP]),
     "boxmot_hip_last_error": (ctypes.c_char_p, []),
     "boxmot_hip_device_count": (_I, []),
     "boxmot_hip_botsort_device": (_I, [_VP]),

@@ -25,7 +25,9 @@
 #include "cmc_sof.hpp"
 #include "ingest_nv12.hpp"
 #include "ingest_letterbox.hpp"
+#include "ingest_letterbox_tiles.hpp"
 #include "det_post.hpp"
+#include "det_post_tiled.hpp"
 
 namespace {
 
@@ -317,10 +319,14 @@ struct BoxMOTHipIngest : DeviceBound {
     uint32_t* d_lb_lut[4] = {nullptr, nullptr, nullptr, nullptr};      // [2 * unit + dtype]: the 256 table entries
     std::vector<hipEvent_t> lb_done;                // [n_slots]: the slot's last letterbox launch
     std::vector<char> has_lb;
+    // letterbox of rectangles (csrc/ingest_letterbox_tiles.hpp): per (H, W, mode, rectangles) the [n_streams][n_tiles] geometry
+    struct TileTable { int H, W, mode, n_streams, n_tiles; std::vector<int> rects; bm::LetterboxTileGeom* d_geom; };
+    std::vector<TileTable> lb_tile_tables;
     ~BoxMOTHipIngest() {
         if (copy_stream) (void)hipStreamSynchronize(copy_stream);
         for (auto e : lb_done) { (void)hipEventSynchronize(e); (void)hipEventDestroy(e); }
         for (auto& t : lb_tables) if (t.d_geom) (void)hipFree(t.d_geom);
+        for (auto& t : lb_tile_tables) if (t.d_geom) (void)hipFree(t.d_geom);
         for (auto p : d_lb_lut) if (p) (void)hipFree(p);
         for (auto p : h_slot) if (p) (void)hipHostFree(p);
         for (auto p : d_slot) if (p) (void)hipFree(p);
@@ -350,7 +356,15 @@ struct BoxMOTHipDetPost : DeviceBound {
     std::vector<bm::DetPostGeom> geom;              // what the device table holds
     hipEvent_t done = nullptr;                      // the last run: the next one (on any stream) and counters() wait for it
     bool ran = false;
+    // a tiled handle (boxmot_hip_detpost_create_tiled, csrc/det_post_tiled.hpp): the scratch is [n_streams * n_tiles][n_anchors] and the
+    // geometry is per (stream, tile): d_geom / h_geom / geom above are not used
+    int n_tiles = 0, merge = 0;
+    bm::DetPostTileGeom* d_tgeom = nullptr;         // [n_streams][n_tiles]
+    bm::DetPostTileGeom* h_tgeom[2] = {nullptr, nullptr};
+    std::vector<bm::DetPostTileGeom> tgeom;
     ~BoxMOTHipDetPost() {
+        for (auto p : h_tgeom) if (p) (void)hipHostFree(p);
+        if (d_tgeom) (void)hipFree(d_tgeom);
         if (done) { if (ran) (void)hipEventSynchronize(done); (void)hipEventDestroy(done); }
         for (auto e : geom_copied) if (e) (void)hipEventDestroy(e);
         for (auto p : h_geom) if (p) (void)hipHostFree(p);
@@ -2930,17 +2944,48 @@ static uint32_t letterbox_half_bits(float f) {
     return h;
 }
 
+// what every letterbox launch checks of its arguments before it touches the handle's tables
+static void letterbox_check_call(BoxMOTHipIngest* handle, int slot, int n_streams, const BoxMOTHipLetterbox* cfg, const void* d_out) {
+    ingest_slot(handle, slot);
+    if (n_streams < 1 || n_streams > handle->n_streams) throw std::runtime_error("boxmot_hip: stream count out of range");
+    letterbox_check_config(cfg);
+    if (cfg->dtype != 0 && cfg->dtype != 1) throw std::runtime_error("boxmot_hip: unknown letterbox dtype " + std::to_string(cfg->dtype) + " (0 fp32, 1 fp16)");
+    if (cfg->out_cols % bm::LB_PX) throw std::runtime_error("boxmot_hip: letterbox out_cols must be a multiple of 8, got " + std::to_string(cfg->out_cols));
+    if (cfg->pad_value < 0 || cfg->pad_value > 255) throw std::runtime_error("boxmot_hip: letterbox pad_value must be within 0..255, got " + std::to_string(cfg->pad_value));
+    if (!d_out) throw std::runtime_error("boxmot_hip: null letterbox output");
+    if ((uintptr_t)d_out & 15) throw std::runtime_error("boxmot_hip: the letterbox output must be 16-byte aligned");
+}
+
+// the 256-entry table of (unit, dtype) and the slots' letterbox events, made on first use; returns the table's index in d_lb_lut
+static int letterbox_table_and_events(BoxMOTHipIngest* handle, const BoxMOTHipLetterbox* cfg) {
+    const int which = 2 * (cfg->unit ? 1 : 0) + cfg->dtype;
+    if (!handle->d_lb_lut[which]) {
+        uint32_t lut[256];
+        for (int v = 0; v < 256; ++v) {
+            const float f = cfg->unit ? (float)v / 255.0f : (float)v;
+            if (cfg->dtype) lut[v] = letterbox_half_bits(f);
+            else std::memcpy(&lut[v], &f, 4);
+        }
+        void* lp = nullptr;
+        BM_HIP(hipMalloc(&lp, sizeof(lut)));
+        handle->d_lb_lut[which] = static_cast<uint32_t*>(lp);
+        BM_HIP(hipMemcpy(lp, lut, sizeof(lut), hipMemcpyHostToDevice));
+    }
+    if (handle->lb_done.empty()) {
+        for (int k = 0; k < handle->n_slots; ++k) {
+            hipEvent_t e;
+            BM_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            handle->lb_done.push_back(e);
+        }
+        handle->has_lb.assign(handle->n_slots, 0);
+    }
+    return which;
+}
+
 int boxmot_hip_ingest_letterbox(BoxMOTHipIngest* handle, int slot, int n_streams, const BoxMOTHipLetterbox* cfg, void* d_out,
                                 void* consumer_hip_stream) {
     return guard_on(handle, [&]() {
-        ingest_slot(handle, slot);
-        if (n_streams < 1 || n_streams > handle->n_streams) throw std::runtime_error("boxmot_hip: stream count out of range");
-        letterbox_check_config(cfg);
-        if (cfg->dtype != 0 && cfg->dtype != 1) throw std::runtime_error("boxmot_hip: unknown letterbox dtype " + std::to_string(cfg->dtype) + " (0 fp32, 1 fp16)");
-        if (cfg->out_cols % bm::LB_PX) throw std::runtime_error("boxmot_hip: letterbox out_cols must be a multiple of 8, got " + std::to_string(cfg->out_cols));
-        if (cfg->pad_value < 0 || cfg->pad_value > 255) throw std::runtime_error("boxmot_hip: letterbox pad_value must be within 0..255, got " + std::to_string(cfg->pad_value));
-        if (!d_out) throw std::runtime_error("boxmot_hip: null letterbox output");
-        if ((uintptr_t)d_out & 15) throw std::runtime_error("boxmot_hip: the letterbox output must be 16-byte aligned");
+        letterbox_check_call(handle, slot, n_streams, cfg, d_out);
         const int H = cfg->out_rows, W = cfg->out_cols;
         // the streams' geometry for this (H, W, mode): computed and copied to the device once, so a steady-state call copies nothing
         BoxMOTHipIngest::LetterboxTable* tab = nullptr;
@@ -2966,27 +3011,7 @@ int boxmot_hip_ingest_letterbox(BoxMOTHipIngest* handle, int slot, int n_streams
                 throw std::runtime_error("boxmot_hip: ingest ring stream " + std::to_string(s) + ": letterbox of a " + std::to_string(handle->srows[s]) +
                                          " x " + std::to_string(handle->scols[s]) + " frame into " + std::to_string(H) + " x " + std::to_string(W) +
                                          " leaves no picture (" + std::to_string(tab->geom[s].new_h) + " x " + std::to_string(tab->geom[s].new_w) + ")");
-        const int which = 2 * (cfg->unit ? 1 : 0) + cfg->dtype;
-        if (!handle->d_lb_lut[which]) {
-            uint32_t lut[256];
-            for (int v = 0; v < 256; ++v) {
-                const float f = cfg->unit ? (float)v / 255.0f : (float)v;
-                if (cfg->dtype) lut[v] = letterbox_half_bits(f);
-                else std::memcpy(&lut[v], &f, 4);
-            }
-            void* lp = nullptr;
-            BM_HIP(hipMalloc(&lp, sizeof(lut)));
-            handle->d_lb_lut[which] = static_cast<uint32_t*>(lp);
-            BM_HIP(hipMemcpy(lp, lut, sizeof(lut), hipMemcpyHostToDevice));
-        }
-        if (handle->lb_done.empty()) {
-            for (int k = 0; k < handle->n_slots; ++k) {
-                hipEvent_t e;
-                BM_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-                handle->lb_done.push_back(e);
-            }
-            handle->has_lb.assign(handle->n_slots, 0);
-        }
+        const int which = letterbox_table_and_events(handle, cfg);
         hipStream_t st = static_cast<hipStream_t>(consumer_hip_stream);
         BM_HIP(hipStreamWaitEvent(st, handle->uploaded[slot], 0));
         hipLaunchKernelGGL(bm::k_letterbox, dim3((unsigned)bm::letterbox_grid_x(H, W), (unsigned)n_streams), dim3(bm::LB_THREADS), 0, st,
@@ -2998,10 +3023,95 @@ int boxmot_hip_ingest_letterbox(BoxMOTHipIngest* handle, int slot, int n_streams
     });
 }
 
+// ---- letterboxed rectangles of the frames: sliced inference (csrc/ingest_letterbox_tiles.hpp has the definition) ----
+static std::string letterbox_tile_name(int s, int t, const int* r) {
+    return "stream " + std::to_string(s) + " tile " + std::to_string(t) + " (x0 " + std::to_string(r[0]) + ", y0 " + std::to_string(r[1]) + ", w " +
+           std::to_string(r[2]) + ", h " + std::to_string(r[3]) + ")";
+}
+
+int boxmot_hip_letterbox_tile_geometry(int image_rows, int image_cols, const int* rect, const BoxMOTHipLetterbox* cfg, double* out) {
+    return guard([&]() {
+        letterbox_check_config(cfg);
+        if (!out || !rect) throw std::runtime_error("boxmot_hip: null argument");
+        if (image_rows < 1 || image_cols < 1) throw std::runtime_error("boxmot_hip: frame dimensions must be positive");
+        for (int k = 0; k < 9; ++k) out[k] = 0.0;
+        out[5] = rect[3]; out[6] = rect[2]; out[7] = rect[0]; out[8] = rect[1];
+        if (!bm::letterbox_tile_inside(image_rows, image_cols, rect[0], rect[1], rect[2], rect[3]))
+            throw std::runtime_error("boxmot_hip: letterbox rectangle (x0 " + std::to_string(rect[0]) + ", y0 " + std::to_string(rect[1]) + ", w " +
+                                     std::to_string(rect[2]) + ", h " + std::to_string(rect[3]) + ") is not inside the " + std::to_string(image_rows) +
+                                     " x " + std::to_string(image_cols) + " frame");
+        bm::LetterboxTileGeom g;
+        const bool ok = bm::letterbox_tile_geometry(image_cols, rect[0], rect[1], rect[2], rect[3], cfg->out_rows, cfg->out_cols, cfg->mode, &out[0], &g);
+        out[1] = g.g.new_w; out[2] = g.g.new_h; out[3] = g.g.top; out[4] = g.g.left;
+        if (!ok)
+            throw std::runtime_error("boxmot_hip: letterbox of a " + std::to_string(rect[3]) + " x " + std::to_string(rect[2]) + " rectangle into " +
+                                     std::to_string(cfg->out_rows) + " x " + std::to_string(cfg->out_cols) + " leaves no picture (" +
+                                     std::to_string(g.g.new_h) + " x " + std::to_string(g.g.new_w) + ")");
+    });
+}
+
+int boxmot_hip_ingest_letterbox_tiles(BoxMOTHipIngest* handle, int slot, int n_streams, int n_tiles, const int* rects, const BoxMOTHipLetterbox* cfg,
+                                      void* d_out, void* consumer_hip_stream) {
+    return guard_on(handle, [&]() {
+        letterbox_check_call(handle, slot, n_streams, cfg, d_out);
+        if (n_tiles < 1 || n_tiles > bm::LB_TILES_MAX)
+            throw std::runtime_error("boxmot_hip: letterbox n_tiles must be within 1.." + std::to_string(bm::LB_TILES_MAX) + ", got " + std::to_string(n_tiles));
+        if (!rects) throw std::runtime_error("boxmot_hip: null letterbox rectangles");
+        const int H = cfg->out_rows, W = cfg->out_cols;
+        const size_t n = (size_t)n_streams * n_tiles;
+        if (n > 65535) throw std::runtime_error("boxmot_hip: letterbox n_streams * n_tiles must not exceed 65535 (grid.y), got " + std::to_string(n));
+        // every rectangle is checked on every call, before anything is launched: the kernel reads what the table says
+        for (int s = 0; s < n_streams; ++s)
+            for (int t = 0; t < n_tiles; ++t) {
+                const int* r = rects + ((size_t)s * n_tiles + t) * 4;
+                if (!bm::letterbox_tile_inside(handle->srows[s], handle->scols[s], r[0], r[1], r[2], r[3]))
+                    throw std::runtime_error("boxmot_hip: ingest ring " + letterbox_tile_name(s, t, r) + " is not inside the " +
+                                             std::to_string(handle->srows[s]) + " x " + std::to_string(handle->scols[s]) + " frame");
+            }
+        // the geometry of these rectangles for this (H, W, mode): computed and copied to the device once
+        BoxMOTHipIngest::TileTable* tab = nullptr;
+        for (auto& t : handle->lb_tile_tables)
+            if (t.H == H && t.W == W && t.mode == cfg->mode && t.n_streams == n_streams && t.n_tiles == n_tiles &&
+                std::memcmp(t.rects.data(), rects, n * 4 * sizeof(int)) == 0)
+                tab = &t;
+        if (!tab) {
+            std::vector<bm::LetterboxTileGeom> geom(n);
+            for (int s = 0; s < n_streams; ++s)
+                for (int t = 0; t < n_tiles; ++t) {
+                    const int* r = rects + ((size_t)s * n_tiles + t) * 4;
+                    bm::LetterboxTileGeom& g = geom[(size_t)s * n_tiles + t];
+                    if (!bm::letterbox_tile_geometry(handle->scols[s], r[0], r[1], r[2], r[3], H, W, cfg->mode, nullptr, &g))
+                        throw std::runtime_error("boxmot_hip: ingest ring " + letterbox_tile_name(s, t, r) + ": letterbox into " + std::to_string(H) + " x " +
+                                                 std::to_string(W) + " leaves no picture (" + std::to_string(g.g.new_h) + " x " + std::to_string(g.g.new_w) + ")");
+                }
+            if (handle->lb_tile_tables.size() >= 16) {      // a caller that keeps changing the rectangles: drop the oldest (hipFree waits for the device)
+                BM_HIP(hipFree(handle->lb_tile_tables.front().d_geom));
+                handle->lb_tile_tables.erase(handle->lb_tile_tables.begin());
+            }
+            void* dp = nullptr;
+            BM_HIP(hipMalloc(&dp, n * sizeof(bm::LetterboxTileGeom)));
+            const hipError_t copied = hipMemcpy(dp, geom.data(), n * sizeof(bm::LetterboxTileGeom), hipMemcpyHostToDevice);
+            if (copied != hipSuccess) { (void)hipFree(dp); BM_HIP(copied); }
+            handle->lb_tile_tables.push_back(BoxMOTHipIngest::TileTable{H, W, cfg->mode, n_streams, n_tiles, std::vector<int>(rects, rects + n * 4),
+                                                                         static_cast<bm::LetterboxTileGeom*>(dp)});
+            tab = &handle->lb_tile_tables.back();
+        }
+        const int which = letterbox_table_and_events(handle, cfg);
+        hipStream_t st = static_cast<hipStream_t>(consumer_hip_stream);
+        BM_HIP(hipStreamWaitEvent(st, handle->uploaded[slot], 0));
+        hipLaunchKernelGGL(bm::k_letterbox_tiles, dim3((unsigned)bm::letterbox_grid_x(H, W), (unsigned)n), dim3(bm::LB_THREADS), 0, st,
+                           (const uint8_t* const*)handle->d_ptrs[slot], (const bm::LetterboxTileGeom*)tab->d_geom,
+                           (const uint32_t*)handle->d_lb_lut[which], d_out, n_tiles, H, W, cfg->dtype, cfg->rgb ? 1 : 0, cfg->pad_value);
+        BM_HIP(hipGetLastError());
+        BM_HIP(hipEventRecord(handle->lb_done[slot], st));
+        handle->has_lb[slot] = 1;
+    });
+}
+
 // ---- detection post-processing (csrc/det_post.hpp has the definition) ----
 namespace {
-// both create entry points; oc: the oriented options, or null for an axis-aligned handle
-BoxMOTHipDetPost* detpost_create(const BoxMOTHipDetPostConfig* c, const BoxMOTHipDetPostObbConfig* oc) {
+// the create entry points; oc: the oriented options, or null for an axis-aligned handle; tc: the tiled options, or null
+BoxMOTHipDetPost* detpost_create(const BoxMOTHipDetPostConfig* c, const BoxMOTHipDetPostObbConfig* oc, const BoxMOTHipDetPostTiledConfig* tc = nullptr) {
     BoxMOTHipDetPost* h = nullptr;
     const int ok = guard([&]() {
         if (!c) throw std::runtime_error("boxmot_hip: null detpost config");
@@ -3018,12 +3128,20 @@ BoxMOTHipDetPost* detpost_create(const BoxMOTHipDetPostConfig* c, const BoxMOTHi
             throw std::runtime_error("boxmot_hip: detpost max_candidates must be within 64..4096, got " + std::to_string(c->max_candidates));
         if (c->max_det < 1) throw std::runtime_error("boxmot_hip: detpost max_det must be >= 1");
         if ((long)c->n_streams * c->n_anchors > (1L << 30)) throw std::runtime_error("boxmot_hip: detpost n_streams * n_anchors is too large");
+        if (tc && (tc->n_tiles < 1 || tc->n_tiles > bm::DP_TILES_MAX))
+            throw std::runtime_error("boxmot_hip: detpost n_tiles must be within 1.." + std::to_string(bm::DP_TILES_MAX) + ", got " + std::to_string(tc->n_tiles));
+        if (tc && tc->merge != 0 && tc->merge != 1) throw std::runtime_error("boxmot_hip: unknown detpost merge " + std::to_string(tc->merge) + " (0 iou, 1 ios)");
+        const int n_tensors = tc ? tc->n_tiles : 1;         // per stream
+        if ((long)c->n_streams * n_tensors * c->n_anchors > (1L << 30))
+            throw std::runtime_error("boxmot_hip: detpost n_streams * n_tiles * n_anchors is too large");
+        if ((long)c->n_streams * n_tensors > 65535) throw std::runtime_error("boxmot_hip: detpost n_streams * n_tiles must not exceed 65535 (grid.y)");
         require_device();
         h = new BoxMOTHipDetPost();
         h->cfg = *c;
         h->cfg.class_allow = nullptr;
         if (oc) { h->obb = 1; h->nms_mode = oc->nms_mode; h->regularize = oc->regularize ? 1 : 0; }
-        const size_t SA = (size_t)c->n_streams * c->n_anchors;
+        if (tc) { h->n_tiles = tc->n_tiles; h->merge = tc->merge; }
+        const size_t SA = (size_t)c->n_streams * n_tensors * c->n_anchors;
         void* p = nullptr;
         BM_HIP(hipMalloc(&p, SA * sizeof(uint32_t))); h->d_keys = static_cast<uint32_t*>(p);
         BM_HIP(hipMalloc(&p, SA * sizeof(int))); h->d_cls = static_cast<int*>(p);
@@ -3044,7 +3162,18 @@ BoxMOTHipDetPost* detpost_create(const BoxMOTHipDetPostConfig* c, const BoxMOTHi
         }
         BM_HIP(hipEventCreateWithFlags(&h->done, hipEventDisableTiming));
         // the workgroup's LDS grows with max_candidates and passes the 64 KB a kernel may take without saying so
-        if (oc) {
+        if (tc) {
+            const size_t ST = (size_t)c->n_streams * tc->n_tiles;
+            BM_HIP(hipMalloc(&p, ST * sizeof(bm::DetPostTileGeom))); h->d_tgeom = static_cast<bm::DetPostTileGeom*>(p);
+            for (int k = 0; k < 2; ++k) {
+                BM_HIP(hipHostMalloc(&p, ST * sizeof(bm::DetPostTileGeom), hipHostMallocDefault));
+                h->h_tgeom[k] = static_cast<bm::DetPostTileGeom*>(p);
+            }
+            h->tgeom.resize(ST);
+            const int lds = (int)bm::detpost_lds_bytes(c->max_candidates);
+            BM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(bm::k_detpost_select_tiled<float>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+            BM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(bm::k_detpost_select_tiled<_Float16>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        } else if (oc) {
             const int lds = (int)bm::detpost_obb_lds_bytes(c->max_candidates);
             BM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(bm::k_detpost_select_obb<float>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
             BM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(bm::k_detpost_select_obb<_Float16>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
@@ -3073,6 +3202,7 @@ int boxmot_hip_detpost_run(BoxMOTHipDetPost* handle, int n_streams, const void* 
     return guard_on(handle, [&]() {
         if (!handle) throw std::runtime_error("boxmot_hip: null detpost handle");
         const BoxMOTHipDetPostConfig& c = handle->cfg;
+        if (handle->n_tiles) throw std::runtime_error("boxmot_hip: a tiled detpost handle is run with boxmot_hip_detpost_run_tiled");
         if (n_streams < 1 || n_streams > c.n_streams)
             throw std::runtime_error("boxmot_hip: detpost stream count " + std::to_string(n_streams) + " out of range for a handle of " + std::to_string(c.n_streams));
         if (!d_pred || !geom || !d_dets || !d_det_rows) throw std::runtime_error("boxmot_hip: null detpost argument");
@@ -3109,6 +3239,64 @@ int boxmot_hip_detpost_run(BoxMOTHipDetPost* handle, int n_streams, const void* 
                           handle->obb, handle->nms_mode, handle->regularize};
         DetPostLaunch launch{st};
         bm::detpost_launch(launch, a, n_streams, dtype);
+        BM_HIP(hipGetLastError());
+        BM_HIP(hipEventRecord(handle->done, st));
+        handle->ran = true;
+    });
+}
+
+BoxMOTHipDetPost* boxmot_hip_detpost_create_tiled(const BoxMOTHipDetPostTiledConfig* c) {
+    if (!c) { g_last_error = "boxmot_hip: null detpost config"; return nullptr; }
+    return detpost_create(&c->base, nullptr, c);
+}
+
+int boxmot_hip_detpost_run_tiled(BoxMOTHipDetPost* handle, int n_streams, const void* d_pred, int dtype, const double* geom, float* d_dets,
+                                 int out_stride_rows, int* d_det_rows, void* hip_stream) {
+    return guard_on(handle, [&]() {
+        if (!handle) throw std::runtime_error("boxmot_hip: null detpost handle");
+        const BoxMOTHipDetPostConfig& c = handle->cfg;
+        if (!handle->n_tiles) throw std::runtime_error("boxmot_hip: boxmot_hip_detpost_run_tiled needs a handle of boxmot_hip_detpost_create_tiled");
+        if (n_streams < 1 || n_streams > c.n_streams)
+            throw std::runtime_error("boxmot_hip: detpost stream count " + std::to_string(n_streams) + " out of range for a handle of " + std::to_string(c.n_streams));
+        if (!d_pred || !geom || !d_dets || !d_det_rows) throw std::runtime_error("boxmot_hip: null detpost argument");
+        if (dtype != 0 && dtype != 1) throw std::runtime_error("boxmot_hip: unknown detpost dtype " + std::to_string(dtype) + " (0 fp32, 1 fp16)");
+        if ((uintptr_t)d_pred % (dtype ? 2 : 4) || (uintptr_t)d_dets % 4 || (uintptr_t)d_det_rows % 4)
+            throw std::runtime_error("boxmot_hip: detpost device addresses must be aligned to their element size");
+        if (out_stride_rows < c.max_det)
+            throw std::runtime_error("boxmot_hip: detpost out_stride_rows " + std::to_string(out_stride_rows) + " is below max_det " + std::to_string(c.max_det));
+        const int T = handle->n_tiles;
+        const size_t n = (size_t)n_streams * T;
+        std::vector<bm::DetPostTileGeom> g(n);
+        bool same = n_streams <= handle->geom_valid;
+        for (size_t k = 0; k < n; ++k) {
+            const double* v = geom + 7 * k;
+            bool finite = true;
+            for (int q = 0; q < 7; ++q) finite = finite && std::isfinite(v[q]);
+            if (!finite || !(v[0] > 0.0) || !(v[5] >= 1.0) || !(v[6] >= 1.0))
+                throw std::runtime_error("boxmot_hip: detpost stream " + std::to_string(k / T) + " tile " + std::to_string(k % T) +
+                                         ": geometry needs finite values, gain > 0 and a tile of >= 1 x 1 (gain " + std::to_string(v[0]) + ", w " +
+                                         std::to_string(v[5]) + ", h " + std::to_string(v[6]) + ")");
+            g[k] = bm::DetPostTileGeom{(float)v[0], (float)v[1], (float)v[2], (float)v[3], (float)v[4], (float)v[5], (float)v[6]};
+            if (same && std::memcmp(&g[k], &handle->tgeom[k], sizeof(bm::DetPostTileGeom)) != 0) same = false;
+        }
+        hipStream_t st = static_cast<hipStream_t>(hip_stream);
+        if (handle->ran) BM_HIP(hipStreamWaitEvent(st, handle->done, 0));      // the scratch and the table are the handle's
+        if (!same) {
+            const int k = handle->geom_uploads & 1;
+            if (handle->geom_uploads >= 2) BM_HIP(hipEventSynchronize(handle->geom_copied[k]));    // (two uploads ago: long done)
+            std::memcpy(handle->h_tgeom[k], g.data(), n * sizeof(bm::DetPostTileGeom));
+            BM_HIP(hipMemcpyAsync(handle->d_tgeom, handle->h_tgeom[k], n * sizeof(bm::DetPostTileGeom), hipMemcpyHostToDevice, st));
+            BM_HIP(hipEventRecord(handle->geom_copied[k], st));
+            handle->geom_uploads += 1;
+            std::copy(g.begin(), g.end(), handle->tgeom.begin());
+            if (handle->geom_valid < n_streams) handle->geom_valid = n_streams;
+        }
+        bm::DetPostTiledArgs a{bm::DetPostArgs{d_pred, nullptr, handle->d_allow, handle->d_keys, handle->d_cls, d_dets, d_det_rows, handle->d_counters,
+                                               c.n_anchors, c.n_classes, c.layout, c.max_candidates, c.max_det, c.agnostic ? 1 : 0, out_stride_rows,
+                                               c.conf_thres, c.iou_thres, 0, 0, 0},
+                               handle->d_tgeom, T, handle->merge};
+        DetPostLaunch launch{st};
+        bm::detpost_launch_tiled(launch, a, n_streams, dtype);
         BM_HIP(hipGetLastError());
         BM_HIP(hipEventRecord(handle->done, st));
         handle->ran = true;

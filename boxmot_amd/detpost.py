@@ -19,6 +19,22 @@ the last row -- and writes 7-column rows ``[cx, cy, w, h, angle, conf, cls]``, n
 reads through ``step_device`` (the definition is at the top of csrc/det_post_obb.hpp).  The NMS is rotated, by the ProbIoU closed
 form in float32, ``ProbIoU >= iou`` suppresses; ``nms="greedy"`` drops a candidate that an earlier KEPT one suppresses,
 ``nms="fast"`` one that ANY earlier one suppresses (what Ultralytics ``nms_rotated`` computes).
+
+Tiled detection for large frames (sliced inference): ``DetPost(..., tiles=T, merge="iou" | "ios")`` reads the detector's output on
+the ``T`` tiles per stream that ``FrameRing.letterbox_tiles`` wrote -- ``pred`` is (S * T, ...), tile ``t`` of stream ``s`` at index
+``s * T + t`` -- and merges them with ONE NMS per stream in frame coordinates (the definition is at the top of
+csrc/det_post_tiled.hpp):
+
+    tiles = tile_grid(2160, 3840, grid=(2, 3), overlap=0.2)              # the whole frame and 2 x 3 tiles: T = 7
+    post = DetPost(S, n_anchors=8400, n_classes=80, tiles=len(tiles), merge="ios")
+    geo = ring.letterbox_tiles(k, x, tiles, hip_stream=st)               # x: (S * 7, 3, 640, 640)
+    post.run(my_detector(x), geo, d_dets, d_rows, hip_stream=st)
+
+Stated plainly: the ``max_candidates`` best anchors of all of a stream's tiles by (conf descending, tile ascending, anchor
+ascending) are mapped to the frame -- ``clip((x - left) / gain, 0, w) + x0`` -- BEFORE a merged greedy NMS in float32;
+``merge="iou"`` suppresses on ``IoU > iou``, ``merge="ios"`` on ``inter / min(area_i, area_j) > iou`` (intersection over the
+smaller box: a box cut by a tile's edge is absorbed by the whole one).  It is pinned against this repository's NumPy restatement
+(tests/detpost_tiled_ref.py) only, not against SAHI or Ultralytics.
 """
 from __future__ import annotations
 
@@ -30,6 +46,8 @@ from boxmot_amd import _lib
 
 LAYOUTS = {"cn": 0, "nc_obj": 1, "cn_obb": 0}          # the C ABI's layout code: "cn_obb" is "cn" through boxmot_hip_detpost_create_obb
 NMS_MODES = {"greedy": 0, "fast": 1}
+MERGES = {"iou": 0, "ios": 1}
+MAX_TILES = 64
 _DTYPES = {"float32": 0, "float16": 1}
 
 
@@ -51,18 +69,36 @@ def _geometry_row(g, s):
     return row
 
 
+def _tile_geometry_row(g, s, t):
+    """(gain, top, left, x0, y0, w, h) of a ``TileGeometry`` (or of a 7-sequence in that order)"""
+    what = f"stream {s} tile {t}: geometry must be a TileGeometry or (gain, top, left, x0, y0, w, h), got {g!r}"
+    try:
+        row = (g.gain, g.top, g.left, g.x0, g.y0, g.cols, g.rows) if hasattr(g, "gain") else tuple(g)
+        row = tuple(float(v) for v in row)
+    except (TypeError, ValueError, AttributeError):
+        raise ValueError(what) from None
+    if len(row) != 7:
+        raise ValueError(what)
+    if not all(np.isfinite(row)) or not row[0] > 0 or row[5] < 1 or row[6] < 1:
+        raise ValueError(f"stream {s} tile {t}: geometry needs finite values, gain > 0 and a tile of at least 1 x 1, got gain {row[0]}, w {row[5]}, "
+                         f"h {row[6]}")
+    return row
+
+
 class DetPost:
     def __init__(self, n_streams: int, n_anchors: int, n_classes: int, layout: str = "cn", conf: float = 0.25, iou: float = 0.45,
                  max_det: int = 256, max_candidates: int = 1024, agnostic: bool = False, classes=None, nms: str | None = None,
-                 regularize: bool | None = None):
+                 regularize: bool | None = None, tiles: int | None = None, merge: str | None = None):
         """``layout``: ``"cn"`` -- (S, 4 + n_classes, n_anchors), the Ultralytics v8 / 11 raw head, conf = the best class score --
         ``"nc_obj"`` -- (S, n_anchors, 5 + n_classes), the YOLOX / YOLOv5 decoded head, conf = obj * the best class score -- or
         ``"cn_obb"`` -- (S, 4 + n_classes + 1, n_anchors), the Ultralytics OBB raw head, the angle in radians as the last row.
         ``classes``: an optional allow-list of class indices, applied to an anchor's best class.  ``nms`` (``"greedy"``, the
         default, or ``"fast"``) and ``regularize`` (w >= h and the angle within [0, pi] in the rows; default off) belong to
-        ``"cn_obb"`` alone."""
+        ``"cn_obb"`` alone.  ``tiles``: the detector ran on that many tiles per stream (``FrameRing.letterbox_tiles``) and their
+        detections are merged by one NMS per stream in frame coordinates, on ``merge="iou"`` (the default) or ``"ios"``,
+        intersection over the smaller box; ``n_anchors`` stays the anchors of ONE tile tensor.  Not for ``"cn_obb"``."""
         self._handle = None
-        self._configure(n_streams, n_anchors, n_classes, layout, conf, iou, max_det, max_candidates, agnostic, classes, nms, regularize)
+        self._configure(n_streams, n_anchors, n_classes, layout, conf, iou, max_det, max_candidates, agnostic, classes, nms, regularize, tiles, merge)
         self._lib = _lib.load()
         allow = None
         if self.classes is not None:
@@ -70,7 +106,10 @@ class DetPost:
             allow[self.classes] = 1
         cfg = _lib.DetPostConfig(self.n_streams, self.n_anchors, self.n_classes, LAYOUTS[self.layout], self.conf, self.iou, self.max_candidates,
                                  self.max_det, int(self.agnostic), None if allow is None else allow.ctypes.data)
-        if self.is_obb:
+        if self.tiles is not None:
+            tcfg = _lib.DetPostTiledConfig(cfg, self.tiles, MERGES[self.merge])
+            self._handle = self._lib.boxmot_hip_detpost_create_tiled(ctypes.byref(tcfg))
+        elif self.is_obb:
             ocfg = _lib.DetPostObbConfig(cfg, NMS_MODES[self.nms], int(self.regularize))
             self._handle = self._lib.boxmot_hip_detpost_create_obb(ctypes.byref(ocfg))
         else:
@@ -79,7 +118,7 @@ class DetPost:
             raise RuntimeError(_lib.last_error())
 
     def _configure(self, n_streams, n_anchors, n_classes, layout="cn", conf=0.25, iou=0.45, max_det=256, max_candidates=1024, agnostic=False,
-                   classes=None, nms=None, regularize=None):
+                   classes=None, nms=None, regularize=None, tiles=None, merge=None):
         """the options, checked; touches neither the library nor a device"""
         for name, v in (("n_streams", n_streams), ("n_anchors", n_anchors), ("n_classes", n_classes), ("max_det", max_det)):
             if int(v) != v or int(v) < 1:
@@ -89,6 +128,16 @@ class DetPost:
         is_obb = layout == "cn_obb"
         if not is_obb and (nms is not None or regularize is not None):
             raise ValueError(f"DetPost: nms= and regularize= belong to layout \"cn_obb\", not to {layout!r}")
+        if tiles is None and merge is not None:
+            raise ValueError("DetPost: merge= belongs to a tiled handle: give tiles= as well")
+        if tiles is not None:
+            if is_obb:
+                raise ValueError("DetPost: layout \"cn_obb\" has no tiled form: tiles= is for \"cn\" and \"nc_obj\"")
+            if int(tiles) != tiles or not 1 <= int(tiles) <= MAX_TILES:
+                raise ValueError(f"DetPost: tiles must be an integer within 1..{MAX_TILES}, got {tiles!r}")
+            merge = "iou" if merge is None else merge
+            if merge not in MERGES:
+                raise ValueError(f"DetPost: unknown merge {merge!r} (\"iou\" or \"ios\")")
         nms = "greedy" if nms is None else nms
         if nms not in NMS_MODES:
             raise ValueError(f"DetPost: unknown nms {nms!r} (\"greedy\" or \"fast\")")
@@ -109,9 +158,10 @@ class DetPost:
         self.is_obb, self.nms, self.regularize = is_obb, nms if is_obb else None, bool(regularize) if is_obb else None
         self.n_channels = 5 + self.n_classes if is_obb or layout == "nc_obj" else 4 + self.n_classes       # per anchor, in the layout
         self.det_cols = 7 if is_obb else 6
+        self.tiles, self.merge = (None, None) if tiles is None else (int(tiles), merge)
 
     def pred_shape(self, n: int | None = None) -> tuple:
-        n = self.n_streams if n is None else n
+        n = (self.n_streams if n is None else n) * (self.tiles or 1)
         return (n, self.n_anchors, self.n_channels) if self.layout == "nc_obj" else (n, self.n_channels, self.n_anchors)
 
     def _check_run(self, pred, geo, d_dets, d_det_rows):
@@ -119,9 +169,14 @@ class DetPost:
         n = len(geo)
         if not 1 <= n <= self.n_streams:
             raise ValueError(f"DetPost.run: geo has {n} entries for a handle of {self.n_streams} streams")
+        T = self.tiles or 1
+        if self.tiles is not None:
+            for s, g in enumerate(geo):
+                if hasattr(g, "gain") or not hasattr(g, "__len__") or len(g) != T:
+                    raise ValueError(f"DetPost.run: stream {s}: a handle of tiles={T} takes a list of {T} TileGeometry per stream, got {g!r}")
         shape = tuple(int(v) for v in pred.shape)
-        if len(shape) != 3 or shape[0] < n or shape[1:] != self.pred_shape()[1:]:
-            raise ValueError(f"DetPost.run: pred must have shape {('N >= %d' % n,) + self.pred_shape()[1:]} for layout {self.layout!r}, got {shape}")
+        if len(shape) != 3 or shape[0] < n * T or shape[1:] != self.pred_shape()[1:]:
+            raise ValueError(f"DetPost.run: pred must have shape {('N >= %d' % (n * T),) + self.pred_shape()[1:]} for layout {self.layout!r}, got {shape}")
         dtype = _DTYPES.get(_dtype_name(pred))
         if dtype is None:
             raise ValueError(f"DetPost.run: pred must be float16 or float32, got {pred.dtype}")
@@ -146,7 +201,10 @@ class DetPost:
         for name, t in (("pred", pred), ("d_dets", d_dets), ("d_det_rows", d_det_rows)):
             if not int(t.data_ptr()):
                 raise ValueError(f"DetPost.run: {name} has a null device address")
-        table = np.array([_geometry_row(g, s) for s, g in enumerate(geo)], dtype=np.float64)
+        if self.tiles is not None:
+            table = np.array([[_tile_geometry_row(g, s, t) for t, g in enumerate(gs)] for s, gs in enumerate(geo)], dtype=np.float64)
+        else:
+            table = np.array([_geometry_row(g, s) for s, g in enumerate(geo)], dtype=np.float64)
         return n, dtype, table, dshape[1]
 
     def run(self, pred, geo, d_dets, d_det_rows, hip_stream: int = 0) -> None:
@@ -155,11 +213,14 @@ class DetPost:
         ``FrameRing.letterbox`` returned for them; ``d_dets``: (N, rows >= max_det, 6) float32, ``d_det_rows``: (N,) int32, on the
         same device.  Asynchronous on ``hip_stream``: rows ``[x1, y1, x2, y2, conf, cls]`` in frame coordinates and their count per
         stream; rows at and beyond the count, and streams beyond ``len(geo)``, are left alone.  Layout ``"cn_obb"``: ``d_dets`` is
-        (N, rows >= max_det, 7), rows ``[cx, cy, w, h, angle, conf, cls]``, not clipped to the frame."""
+        (N, rows >= max_det, 7), rows ``[cx, cy, w, h, angle, conf, cls]``, not clipped to the frame.  A handle of ``tiles=T``:
+        ``pred`` holds ``len(geo) * T`` tensors and ``geo`` is what ``FrameRing.letterbox_tiles`` returned, per stream a list of
+        ``T`` ``TileGeometry`` (or 7-sequences gain, top, left, x0, y0, w, h); ``d_dets`` / ``d_det_rows`` stay per stream."""
         n, dtype, table, stride = self._check_run(pred, geo, d_dets, d_det_rows)
-        _lib.check(self._lib.boxmot_hip_detpost_run(self._handle, n, ctypes.c_void_p(int(pred.data_ptr())), dtype,
-                                                    table.ctypes.data_as(_lib.c_double_p), ctypes.c_void_p(int(d_dets.data_ptr())), stride,
-                                                    ctypes.c_void_p(int(d_det_rows.data_ptr())), ctypes.c_void_p(int(hip_stream))))
+        run = self._lib.boxmot_hip_detpost_run if self.tiles is None else self._lib.boxmot_hip_detpost_run_tiled
+        _lib.check(run(self._handle, n, ctypes.c_void_p(int(pred.data_ptr())), dtype,
+                       table.ctypes.data_as(_lib.c_double_p), ctypes.c_void_p(int(d_dets.data_ptr())), stride,
+                       ctypes.c_void_p(int(d_det_rows.data_ptr())), ctypes.c_void_p(int(hip_stream))))
 
     def run_host(self, pred, geo) -> list:
         """Convenience form: ``pred`` a device tensor or a host array (uploaded); returns the rows of each stream as an (n_s, 6)

@@ -32,11 +32,20 @@ detector's boxes back to frame coordinates:
     dets = [g.to_frame(d) for g, d in zip(geo, my_detector(x))]       # the caller's detector and NMS
     rows = tracker.update_batch(dets, ring=ring, slot=k)
 
+Large frames (a 4K frame shrinks six times on its way into 640 x 640): ``letterbox_tiles`` letterboxes ``T`` rectangles of every frame
+-- ``tile_grid`` makes an overlapping grid, optionally with the whole frame as tile 0 -- as one batch of ``S * T`` tensors, and
+``DetPost(tiles=T)`` merges the per-tile detections with one NMS per stream in frame coordinates:
+
+    tiles = tile_grid(2160, 3840, grid=(2, 3), overlap=0.2)            # T = 7
+    x = torch.empty((S * 7, 3, 640, 640), dtype=torch.float16, device="cuda")
+    geo = ring.letterbox_tiles(k, x, tiles, hip_stream=st)             # per stream a list of TileGeometry
+
 Everything is a thin ctypes wrapper over boxmot_hip_ingest_* (include/boxmot_hip.h).
 """
 from __future__ import annotations
 
 import ctypes
+import math
 import sys
 from typing import NamedTuple
 
@@ -100,6 +109,90 @@ def letterbox_geometry(rows: int, cols: int, size, mode: str = "center") -> Lett
     if new_w < 1 or new_h < 1:
         raise ValueError(f"letterbox of a {rows} x {cols} frame into {H} x {W} leaves no picture ({new_h} x {new_w})")
     return LetterboxGeometry(gain, new_w, new_h, top, left, rows, cols)
+
+
+MAX_TILES = 64
+
+
+class TileGeometry(NamedTuple):
+    """Where the rectangle ``(x0, y0, cols, rows)`` of a frame lies inside an (H, W) letterboxed tensor: the rectangle is resized by
+    ``gain`` to (new_h, new_w) and placed with its corner at (top, left).  ``rows, cols`` is the RECTANGLE's size (its h, w)."""
+    gain: float
+    new_w: int
+    new_h: int
+    top: int
+    left: int
+    rows: int
+    cols: int
+    x0: int
+    y0: int
+
+    def to_frame(self, boxes) -> np.ndarray:
+        """Detector-space ``xyxy`` of this tile (columns 0..3 of an (N, >= 4) table) -> FRAME coordinates:
+        ``clip((x - left) / gain, 0, cols) + x0`` and ``clip((y - top) / gain, 0, rows) + y0``, in float32 -- the arithmetic of
+        the tiled ``DetPost``.  Other columns are untouched; the input is not modified."""
+        b = np.array(boxes, dtype=np.float32, ndmin=2)
+        if b.shape[-1] < 4:
+            raise ValueError(f"to_frame: boxes need at least the 4 xyxy columns, got shape {b.shape}")
+        gain = np.float32(self.gain)
+        b[:, [0, 2]] = np.clip((b[:, [0, 2]] - np.float32(self.left)) / gain, np.float32(0), np.float32(self.cols)) + np.float32(self.x0)
+        b[:, [1, 3]] = np.clip((b[:, [1, 3]] - np.float32(self.top)) / gain, np.float32(0), np.float32(self.rows)) + np.float32(self.y0)
+        return b
+
+
+def _tile_axis(L: int, n: int, o: float):
+    if n == 1:
+        return L, [0]
+    size = min(L, math.ceil(L / (n - (n - 1) * o)))
+    return size, [(i * (L - size)) // (n - 1) for i in range(n)]
+
+
+def tile_grid(rows: int, cols: int, grid=(2, 2), overlap: float = 0.2, full: bool = True) -> list:
+    """The rectangles ``(x0, y0, w, h)`` of an ``ny x nx`` grid of equal, overlapping tiles over a (rows, cols) frame, row-major,
+    preceded by the whole frame ``(0, 0, cols, rows)`` when ``full`` -- what ``FrameRing.letterbox_tiles`` takes.  Per axis of
+    length L with n tiles: ``size = min(L, ceil(L / (n - (n - 1) * overlap)))``, ``origin_i = (i * (L - size)) // (n - 1)``: the
+    first tile starts at 0, the last ends at L, neighbours share about ``overlap`` of a tile.  The count, ``ny * nx + full``, does
+    not depend on the frame size, so streams of different sizes share a call."""
+    rows, cols = int(rows), int(cols)
+    if rows < 1 or cols < 1:
+        raise ValueError(f"tile_grid: frame dimensions must be positive, got {(rows, cols)}")
+    try:
+        ny, nx = (int(v) for v in grid)
+    except (TypeError, ValueError):
+        raise ValueError(f"tile_grid: grid must be (ny, nx), got {grid!r}") from None
+    if ny < 1 or nx < 1 or ny > rows or nx > cols:
+        raise ValueError(f"tile_grid: grid {(ny, nx)} must be at least (1, 1) and at most the frame size {(rows, cols)}")
+    overlap = float(overlap)
+    if not 0.0 <= overlap <= 0.9:
+        raise ValueError(f"tile_grid: overlap must be within [0, 0.9], got {overlap}")
+    if ny * nx + bool(full) > MAX_TILES:
+        raise ValueError(f"tile_grid: {ny * nx + bool(full)} tiles, more than the {MAX_TILES} a call takes")
+    h, ys = _tile_axis(rows, ny, overlap)
+    w, xs = _tile_axis(cols, nx, overlap)
+    tiles = [(0, 0, cols, rows)] if full else []
+    return tiles + [(x, y, w, h) for y in ys for x in xs]
+
+
+def _tile_rect(r, s, t, rows, cols):
+    try:
+        rect = tuple(int(v) for v in r)
+        exact = len(rect) == 4 and all(float(a) == b for a, b in zip(r, rect))
+    except (TypeError, ValueError):
+        exact = False
+    if not exact:
+        raise ValueError(f"stream {s} tile {t}: a tile is four integers (x0, y0, w, h), got {r!r}")
+    x0, y0, w, h = rect
+    if w < 1 or h < 1 or x0 < 0 or y0 < 0 or x0 + w > cols or y0 + h > rows:
+        raise ValueError(f"stream {s} tile {t}: rectangle (x0 {x0}, y0 {y0}, w {w}, h {h}) must have w, h >= 1 and lie inside the {rows} x {cols} frame")
+    return rect
+
+
+def tile_geometry(rows: int, cols: int, rect, size, mode: str = "center") -> TileGeometry:
+    """The geometry ``FrameRing.letterbox_tiles`` uses for the rectangle ``rect = (x0, y0, w, h)`` of a (rows, cols) frame:
+    ``letterbox_geometry(h, w, size, mode)`` and the rectangle's origin -- equal to ``boxmot_hip_letterbox_tile_geometry``."""
+    x0, y0, w, h = _tile_rect(rect, 0, 0, int(rows), int(cols))
+    g = letterbox_geometry(h, w, size, mode)
+    return TileGeometry(g.gain, g.new_w, g.new_h, g.top, g.left, h, w, x0, y0)
 
 
 class FrameRing:
@@ -281,6 +374,73 @@ class FrameRing:
         cfg = _lib.Letterbox(H, W, LETTERBOX_MODES[mode], dtype, int(bool(rgb)), int(bool(unit)), pad)
         _lib.check(self._lib.boxmot_hip_ingest_letterbox(self._handle, int(slot), n, ctypes.byref(cfg), ctypes.c_void_p(ptr),
                                                          ctypes.c_void_p(int(hip_stream))))
+        return geo
+
+    def _stream_tiles(self, tiles, n):
+        """per stream the checked rectangles of ``tiles``: one list for all streams, or one list per stream"""
+        try:
+            tiles = list(tiles)
+            one = len(tiles) > 0 and not hasattr(tiles[0][0], "__len__")
+        except (TypeError, IndexError):
+            raise ValueError(f"letterbox_tiles: tiles must be a list of (x0, y0, w, h) or one such list per stream, got {tiles!r}") from None
+        if one:
+            tiles = [tiles] * n
+        elif len(tiles) < n:
+            raise ValueError(f"letterbox_tiles: tiles has {len(tiles)} lists for {n} streams")
+        per = [list(t) for t in tiles[:n]]
+        T = len(per[0])
+        for s, t in enumerate(per):
+            if len(t) != T:
+                raise ValueError(f"stream {s}: {len(t)} tiles where stream 0 has {T}: every stream of a call has the same number")
+        if not 1 <= T <= MAX_TILES:
+            raise ValueError(f"letterbox_tiles: the number of tiles per stream must be within 1..{MAX_TILES}, got {T}")
+        return [[_tile_rect(r, s, t, *self.sizes[s]) for t, r in enumerate(rs)] for s, rs in enumerate(per)]
+
+    def letterbox_tiles(self, slot: int, out, tiles, size=None, mode: str = "center", rgb: bool = True, unit: bool = True, pad: int = 114,
+                        n_streams: int | None = None, hip_stream: int = 0):
+        """Sliced inference on large frames: write the letterboxed detector input of ``T`` rectangles of each of the slot's first
+        ``n_streams`` frames into ``out``, (N >= n_streams * T, 3, H, W), tensor ``s * T + t`` being exactly what ``letterbox``
+        would write for a stand-alone frame equal to that rectangle.  ``tiles``: a list of ``(x0, y0, w, h)`` for all streams
+        (``tile_grid(rows, cols, ...)`` on a uniform ring) or one list per stream; the same ``T`` (1..64) for every stream.
+        Everything else -- ``size``, ``mode``, ``rgb``, ``unit``, ``pad``, the ordering on ``hip_stream`` -- as ``letterbox``.
+        Returns, per stream, the list of the tiles' ``TileGeometry`` -- what ``DetPost(tiles=T).run`` takes."""
+        n = self.n_streams if n_streams is None else int(n_streams)
+        if not 1 <= n <= self.n_streams:
+            raise ValueError(f"letterbox_tiles: n_streams {n} out of range for a ring of {self.n_streams} streams")
+        if mode not in LETTERBOX_MODES:
+            raise ValueError(f"letterbox_tiles: unknown mode {mode!r} (\"center\" or \"topleft\")")
+        rects = self._stream_tiles(tiles, n)
+        T = len(rects[0])
+        shape = tuple(int(v) for v in out.shape)
+        H, W = _letterbox_size(shape[-2:] if size is None else size)
+        if len(shape) != 4 or shape[0] < n * T or shape[1:] != (3, H, W):
+            raise ValueError(f"letterbox_tiles: out must have shape (N >= {n * T}, 3, {H}, {W}), got {shape}")
+        dtype = {"float32": 0, "float16": 1}.get(str(out.dtype).split(".")[-1])
+        if dtype is None:
+            raise ValueError(f"letterbox_tiles: out must be float16 or float32, got {out.dtype}")
+        if not out.is_contiguous():
+            raise ValueError("letterbox_tiles: out must be contiguous")
+        if W % 8:
+            raise ValueError(f"letterbox_tiles: the output width must be a multiple of 8, got {W}")
+        pad = int(pad)
+        if not 0 <= pad <= 255:
+            raise ValueError(f"letterbox_tiles: pad must be within 0..255, got {pad}")
+        ptr = int(out.data_ptr())
+        if not ptr or ptr % 16:
+            raise ValueError(f"letterbox_tiles: out must be a non-null 16-byte aligned device address, got {ptr:#x}")
+        geo = []
+        for s in range(n):
+            geo.append([])
+            for t, (x0, y0, w, h) in enumerate(rects[s]):
+                try:
+                    g = letterbox_geometry(h, w, (H, W), mode)
+                except ValueError as e:
+                    raise ValueError(f"stream {s} tile {t}: {e}") from None
+                geo[s].append(TileGeometry(g.gain, g.new_w, g.new_h, g.top, g.left, h, w, x0, y0))
+        table = np.ascontiguousarray(np.array(rects, dtype=np.int32).reshape(n, T, 4))
+        cfg = _lib.Letterbox(H, W, LETTERBOX_MODES[mode], dtype, int(bool(rgb)), int(bool(unit)), pad)
+        _lib.check(self._lib.boxmot_hip_ingest_letterbox_tiles(self._handle, int(slot), n, T, table.ctypes.data, ctypes.byref(cfg),
+                                                               ctypes.c_void_p(ptr), ctypes.c_void_p(int(hip_stream))))
         return geo
 
     def wait(self, slot: int, consumer_stream: int) -> None:

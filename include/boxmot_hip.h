@@ -436,6 +436,38 @@ typedef struct BoxMOTHipDetPostObbConfig {
 } BoxMOTHipDetPostObbConfig;
 BoxMOTHipDetPost* boxmot_hip_detpost_create_obb(const BoxMOTHipDetPostObbConfig* config);
 
+/* Tiled detection for large frames (sliced inference; csrc/ingest_letterbox_tiles.hpp and csrc/det_post_tiled.hpp have the full
+ * definitions): letterbox n_tiles rectangles of every frame as one batch, run the detector on the batch, merge the per-tile
+ * detections in frame coordinates with one NMS per stream.
+ * ingest_letterbox_tiles: rects is a host array [n_streams][n_tiles][4] = x0, y0, w, h in frame pixels, each inside its stream's
+ * frame with w, h >= 1; 1 <= n_tiles <= 64.  d_out is (n_streams * n_tiles, 3, out_rows, out_cols), tensor s * n_tiles + t being
+ * exactly what ingest_letterbox would write for a stand-alone frame equal to that rectangle (geometry, resize paths, table, pad:
+ * all as above with rows = h, cols = w; taps clamp at the rectangle's edge).  cfg, alignment, ordering and errors as
+ * ingest_letterbox; a rectangle outside the frame or one whose picture would vanish is an error naming the stream and tile.  The
+ * geometry table of a (cfg size, mode, rects) is built on the first call with it and kept on the handle.
+ * letterbox_tile_geometry needs no handle and no device: rect = x0, y0, w, h; out[9] = gain, new_w, new_h, top, left, h, w, x0, y0
+ * (returns 0, with out filled, where the picture would vanish or the rectangle leaves the frame). */
+int boxmot_hip_letterbox_tile_geometry(int image_rows, int image_cols, const int* rect, const BoxMOTHipLetterbox* cfg, double* out);
+int boxmot_hip_ingest_letterbox_tiles(BoxMOTHipIngest* handle, int slot, int n_streams, int n_tiles, const int* rects, const BoxMOTHipLetterbox* cfg,
+                                      void* d_out, void* consumer_hip_stream);
+/* Tiled post-processing: base as boxmot_hip_detpost_create (layouts 0 and 1; base.n_streams counts STREAMS, base.n_anchors the
+ * anchors of one tile tensor).  d_pred is (n_streams * n_tiles, ...) with tile t of stream s at index s * n_tiles + t.  The
+ * max_candidates best of a stream's n_tiles * n_anchors anchors by (conf descending, tile ascending, anchor ascending), exactly;
+ * their boxes are mapped to the frame BEFORE the NMS -- min(max((x - left) / gain, 0), w) + x0, likewise y with top, h, y0 -- and
+ * the greedy NMS runs on the frame-space boxes; merge 0 "iou": inter / (area_i + area_j - inter) > iou_thres, merge 1 "ios":
+ * inter / min(area_i, area_j) > iou_thres (intersection over the smaller box: a box cut by a tile's edge is absorbed by the whole
+ * one).  Rows and counters as boxmot_hip_detpost_run, per stream.  geom: a host array [n_streams][n_tiles][7] = gain, top, left,
+ * x0, y0, w, h.  A tiled handle is read and destroyed with boxmot_hip_detpost_counters / _destroy; boxmot_hip_detpost_run refuses
+ * it, as run_tiled refuses an untiled one. */
+typedef struct BoxMOTHipDetPostTiledConfig {
+    BoxMOTHipDetPostConfig base;
+    int n_tiles;                     /* 1..64 */
+    int merge;                       /* 0 iou, 1 ios */
+} BoxMOTHipDetPostTiledConfig;
+BoxMOTHipDetPost* boxmot_hip_detpost_create_tiled(const BoxMOTHipDetPostTiledConfig* config);
+int boxmot_hip_detpost_run_tiled(BoxMOTHipDetPost* handle, int n_streams, const void* d_pred, int dtype, const double* geom, float* d_dets,
+                                 int out_stride_rows, int* d_det_rows, void* hip_stream);
+
 /* ------------------------------------------------------------------------------------------------
  * DeepOCSORT (boxmot/trackers/bbox/deepocsort/deepocsort.py:235-492).  The reference has no native backend
  * for this tracker; the entry points follow the BoT-SORT ones above (same buffer, error and ownership
