@@ -341,6 +341,46 @@ struct BoxMOTHipIngest : DeviceBound {
     }
 };
 
+// The geometry table of a detection post-processing handle, G per entry: the device array, what it holds, and the pinned staging
+// of its uploads -- two buffers used in turn, an event each.  A steady-state run finds the table unchanged and copies nothing.
+template <class G>
+struct DetPostGeomTable {
+    G* d = nullptr;                                 // [n of create()]: every stream of the handle
+    G* h[2] = {nullptr, nullptr};
+    hipEvent_t copied[2] = {nullptr, nullptr};
+    int uploads = 0, valid = 0;                     // uploads so far; the streams whose device entries equal `held`
+    std::vector<G> held;
+    DetPostGeomTable() = default;
+    DetPostGeomTable(const DetPostGeomTable&) = delete;
+    DetPostGeomTable& operator=(const DetPostGeomTable&) = delete;
+    void create(size_t n) {
+        void* p = nullptr;
+        BM_HIP(hipMalloc(&p, n * sizeof(G))); d = static_cast<G*>(p);
+        for (int k = 0; k < 2; ++k) {
+            BM_HIP(hipHostMalloc(&p, n * sizeof(G), hipHostMallocDefault)); h[k] = static_cast<G*>(p);
+            BM_HIP(hipEventCreateWithFlags(&copied[k], hipEventDisableTiming));
+        }
+        held.resize(n);
+    }
+    // the entries of the first n_streams streams become g, by a copy on `st` unless the device holds them already
+    void set(const std::vector<G>& g, int n_streams, hipStream_t st) {
+        if (n_streams <= valid && std::memcmp(g.data(), held.data(), g.size() * sizeof(G)) == 0) return;
+        const int k = uploads & 1;
+        if (uploads >= 2) BM_HIP(hipEventSynchronize(copied[k]));      // (two uploads ago: long done)
+        std::memcpy(h[k], g.data(), g.size() * sizeof(G));
+        BM_HIP(hipMemcpyAsync(d, h[k], g.size() * sizeof(G), hipMemcpyHostToDevice, st));
+        BM_HIP(hipEventRecord(copied[k], st));
+        uploads += 1;
+        std::copy(g.begin(), g.end(), held.begin());
+        if (valid < n_streams) valid = n_streams;
+    }
+    ~DetPostGeomTable() {                           // (the handle has waited for its last run)
+        for (auto e : copied) if (e) (void)hipEventDestroy(e);
+        for (auto p : h) if (p) (void)hipHostFree(p);
+        if (d) (void)hipFree(d);
+    }
+};
+
 // Detection post-processing (csrc/det_post.hpp): the handle owns the per-anchor scratch, the geometry table and the counters
 struct BoxMOTHipDetPost : DeviceBound {
     BoxMOTHipDetPostConfig cfg{};
@@ -349,30 +389,19 @@ struct BoxMOTHipDetPost : DeviceBound {
     int* d_cls = nullptr;                           // [n_streams][n_anchors]
     int* d_counters = nullptr;                      // [n_streams][3]
     uint8_t* d_allow = nullptr;                     // [n_classes] or null
-    bm::DetPostGeom* d_geom = nullptr;              // [n_streams]
-    bm::DetPostGeom* h_geom[2] = {nullptr, nullptr};// pinned staging of the geometry uploads, used in turn
-    hipEvent_t geom_copied[2] = {nullptr, nullptr};
-    int geom_uploads = 0, geom_valid = 0;           // uploads so far; the streams whose device entry equals `geom`
-    std::vector<bm::DetPostGeom> geom;              // what the device table holds
     hipEvent_t done = nullptr;                      // the last run: the next one (on any stream) and counters() wait for it
     bool ran = false;
     // a tiled handle (boxmot_hip_detpost_create_tiled, csrc/det_post_tiled.hpp): the scratch is [n_streams * n_tiles][n_anchors] and the
-    // geometry is per (stream, tile): d_geom / h_geom / geom above are not used
+    // geometry is per (stream, tile).  Of the two tables only the one of the handle's kind is created.
     int n_tiles = 0, merge = 0;
-    bm::DetPostTileGeom* d_tgeom = nullptr;         // [n_streams][n_tiles]
-    bm::DetPostTileGeom* h_tgeom[2] = {nullptr, nullptr};
-    std::vector<bm::DetPostTileGeom> tgeom;
+    DetPostGeomTable<bm::DetPostGeom> geom;         // [n_streams]
+    DetPostGeomTable<bm::DetPostTileGeom> tgeom;    // [n_streams][n_tiles]
     ~BoxMOTHipDetPost() {
-        for (auto p : h_tgeom) if (p) (void)hipHostFree(p);
-        if (d_tgeom) (void)hipFree(d_tgeom);
         if (done) { if (ran) (void)hipEventSynchronize(done); (void)hipEventDestroy(done); }
-        for (auto e : geom_copied) if (e) (void)hipEventDestroy(e);
-        for (auto p : h_geom) if (p) (void)hipHostFree(p);
         if (d_keys) (void)hipFree(d_keys);
         if (d_cls) (void)hipFree(d_cls);
         if (d_counters) (void)hipFree(d_counters);
         if (d_allow) (void)hipFree(d_allow);
-        if (d_geom) (void)hipFree(d_geom);
     }
 };
 
@@ -384,6 +413,44 @@ struct DetPostLaunch {          // detpost_launch's launcher: the kernel sequenc
         hipLaunchKernelGGL(kernel, dim3((unsigned)gx, (unsigned)gy), dim3((unsigned)threads), lds_bytes, stream, args...);
     }
 };
+
+// the workgroup's LDS grows with max_candidates and passes the 64 KB a kernel may take without saying so
+template <class K>
+void detpost_allow_lds(K select_f32, K select_f16, size_t lds) {
+    BM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(select_f32), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    BM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(select_f16), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+}
+
+// what both run entry points check before they read their geometry rows; tiled: which of the two was called
+void detpost_check_run(const BoxMOTHipDetPost* handle, bool tiled, int n_streams, const void* d_pred, int dtype, const double* geom, const float* d_dets,
+                       int out_stride_rows, const int* d_det_rows) {
+    if (!handle) throw std::runtime_error("boxmot_hip: null detpost handle");
+    const BoxMOTHipDetPostConfig& c = handle->cfg;
+    if (!tiled && handle->n_tiles) throw std::runtime_error("boxmot_hip: a tiled detpost handle is run with boxmot_hip_detpost_run_tiled");
+    if (tiled && !handle->n_tiles) throw std::runtime_error("boxmot_hip: boxmot_hip_detpost_run_tiled needs a handle of boxmot_hip_detpost_create_tiled");
+    if (n_streams < 1 || n_streams > c.n_streams)
+        throw std::runtime_error("boxmot_hip: detpost stream count " + std::to_string(n_streams) + " out of range for a handle of " + std::to_string(c.n_streams));
+    if (!d_pred || !geom || !d_dets || !d_det_rows) throw std::runtime_error("boxmot_hip: null detpost argument");
+    if (dtype != 0 && dtype != 1) throw std::runtime_error("boxmot_hip: unknown detpost dtype " + std::to_string(dtype) + " (0 fp32, 1 fp16)");
+    if ((uintptr_t)d_pred % (dtype ? 2 : 4) || (uintptr_t)d_dets % 4 || (uintptr_t)d_det_rows % 4)
+        throw std::runtime_error("boxmot_hip: detpost device addresses must be aligned to their element size");
+    if (out_stride_rows < c.max_det)
+        throw std::runtime_error("boxmot_hip: detpost out_stride_rows " + std::to_string(out_stride_rows) + " is below max_det " + std::to_string(c.max_det));
+}
+
+// what both do with their checked geometry rows g: wait for the handle's last run (the scratch and the table are the handle's), bring
+// the table up to date, launch(launcher) -- their own kernel sequence -- and record the run
+template <class G, class Launch>
+void detpost_run(BoxMOTHipDetPost* handle, DetPostGeomTable<G>& table, const std::vector<G>& g, int n_streams, void* hip_stream, const Launch& launch) {
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    if (handle->ran) BM_HIP(hipStreamWaitEvent(st, handle->done, 0));
+    table.set(g, n_streams, st);
+    DetPostLaunch on{st};
+    launch(on);
+    BM_HIP(hipGetLastError());
+    BM_HIP(hipEventRecord(handle->done, st));
+    handle->ran = true;
+}
 }  // namespace
 
 // What the three tracker handles share on the host: the weight blob and ReID engine, the staging tables of the per-stream inputs and
@@ -2982,6 +3049,19 @@ static int letterbox_table_and_events(BoxMOTHipIngest* handle, const BoxMOTHipLe
     return which;
 }
 
+// What the two letterbox entry points do around their own launch, once they have their geometry table.  Before it: the 256-entry
+// table and the events on first use, and the wait for the slot's upload; returns the table.  After it: the slot's letterbox event.
+static const uint32_t* letterbox_before_launch(BoxMOTHipIngest* handle, int slot, const BoxMOTHipLetterbox* cfg, hipStream_t st) {
+    const int which = letterbox_table_and_events(handle, cfg);
+    BM_HIP(hipStreamWaitEvent(st, handle->uploaded[slot], 0));
+    return handle->d_lb_lut[which];
+}
+static void letterbox_after_launch(BoxMOTHipIngest* handle, int slot, hipStream_t st) {
+    BM_HIP(hipGetLastError());
+    BM_HIP(hipEventRecord(handle->lb_done[slot], st));
+    handle->has_lb[slot] = 1;
+}
+
 int boxmot_hip_ingest_letterbox(BoxMOTHipIngest* handle, int slot, int n_streams, const BoxMOTHipLetterbox* cfg, void* d_out,
                                 void* consumer_hip_stream) {
     return guard_on(handle, [&]() {
@@ -3011,15 +3091,12 @@ int boxmot_hip_ingest_letterbox(BoxMOTHipIngest* handle, int slot, int n_streams
                 throw std::runtime_error("boxmot_hip: ingest ring stream " + std::to_string(s) + ": letterbox of a " + std::to_string(handle->srows[s]) +
                                          " x " + std::to_string(handle->scols[s]) + " frame into " + std::to_string(H) + " x " + std::to_string(W) +
                                          " leaves no picture (" + std::to_string(tab->geom[s].new_h) + " x " + std::to_string(tab->geom[s].new_w) + ")");
-        const int which = letterbox_table_and_events(handle, cfg);
         hipStream_t st = static_cast<hipStream_t>(consumer_hip_stream);
-        BM_HIP(hipStreamWaitEvent(st, handle->uploaded[slot], 0));
+        const uint32_t* lut = letterbox_before_launch(handle, slot, cfg, st);
         hipLaunchKernelGGL(bm::k_letterbox, dim3((unsigned)bm::letterbox_grid_x(H, W), (unsigned)n_streams), dim3(bm::LB_THREADS), 0, st,
-                           (const uint8_t* const*)handle->d_ptrs[slot], (const bm::LetterboxGeom*)tab->d_geom, (const uint32_t*)handle->d_lb_lut[which],
-                           d_out, H, W, cfg->dtype, cfg->rgb ? 1 : 0, cfg->pad_value);
-        BM_HIP(hipGetLastError());
-        BM_HIP(hipEventRecord(handle->lb_done[slot], st));
-        handle->has_lb[slot] = 1;
+                           (const uint8_t* const*)handle->d_ptrs[slot], (const bm::LetterboxGeom*)tab->d_geom, lut, d_out, H, W, cfg->dtype,
+                           cfg->rgb ? 1 : 0, cfg->pad_value);
+        letterbox_after_launch(handle, slot, st);
     });
 }
 
@@ -3096,15 +3173,12 @@ int boxmot_hip_ingest_letterbox_tiles(BoxMOTHipIngest* handle, int slot, int n_s
                                                                          static_cast<bm::LetterboxTileGeom*>(dp)});
             tab = &handle->lb_tile_tables.back();
         }
-        const int which = letterbox_table_and_events(handle, cfg);
         hipStream_t st = static_cast<hipStream_t>(consumer_hip_stream);
-        BM_HIP(hipStreamWaitEvent(st, handle->uploaded[slot], 0));
+        const uint32_t* lut = letterbox_before_launch(handle, slot, cfg, st);
         hipLaunchKernelGGL(bm::k_letterbox_tiles, dim3((unsigned)bm::letterbox_grid_x(H, W), (unsigned)n), dim3(bm::LB_THREADS), 0, st,
-                           (const uint8_t* const*)handle->d_ptrs[slot], (const bm::LetterboxTileGeom*)tab->d_geom,
-                           (const uint32_t*)handle->d_lb_lut[which], d_out, n_tiles, H, W, cfg->dtype, cfg->rgb ? 1 : 0, cfg->pad_value);
-        BM_HIP(hipGetLastError());
-        BM_HIP(hipEventRecord(handle->lb_done[slot], st));
-        handle->has_lb[slot] = 1;
+                           (const uint8_t* const*)handle->d_ptrs[slot], (const bm::LetterboxTileGeom*)tab->d_geom, lut, d_out, n_tiles, H, W,
+                           cfg->dtype, cfg->rgb ? 1 : 0, cfg->pad_value);
+        letterbox_after_launch(handle, slot, st);
     });
 }
 
@@ -3147,13 +3221,6 @@ BoxMOTHipDetPost* detpost_create(const BoxMOTHipDetPostConfig* c, const BoxMOTHi
         BM_HIP(hipMalloc(&p, SA * sizeof(int))); h->d_cls = static_cast<int*>(p);
         BM_HIP(hipMalloc(&p, (size_t)c->n_streams * bm::DP_COUNTERS * sizeof(int))); h->d_counters = static_cast<int*>(p);
         BM_HIP(hipMemset(h->d_counters, 0, (size_t)c->n_streams * bm::DP_COUNTERS * sizeof(int)));
-        BM_HIP(hipMalloc(&p, (size_t)c->n_streams * sizeof(bm::DetPostGeom))); h->d_geom = static_cast<bm::DetPostGeom*>(p);
-        for (int k = 0; k < 2; ++k) {
-            BM_HIP(hipHostMalloc(&p, (size_t)c->n_streams * sizeof(bm::DetPostGeom), hipHostMallocDefault));
-            h->h_geom[k] = static_cast<bm::DetPostGeom*>(p);
-            BM_HIP(hipEventCreateWithFlags(&h->geom_copied[k], hipEventDisableTiming));
-        }
-        h->geom.resize(c->n_streams);
         if (c->class_allow) {
             std::vector<uint8_t> allow(c->n_classes);
             for (int k = 0; k < c->n_classes; ++k) allow[k] = c->class_allow[k] ? 1 : 0;
@@ -3161,26 +3228,13 @@ BoxMOTHipDetPost* detpost_create(const BoxMOTHipDetPostConfig* c, const BoxMOTHi
             BM_HIP(hipMemcpy(h->d_allow, allow.data(), allow.size(), hipMemcpyHostToDevice));
         }
         BM_HIP(hipEventCreateWithFlags(&h->done, hipEventDisableTiming));
-        // the workgroup's LDS grows with max_candidates and passes the 64 KB a kernel may take without saying so
         if (tc) {
-            const size_t ST = (size_t)c->n_streams * tc->n_tiles;
-            BM_HIP(hipMalloc(&p, ST * sizeof(bm::DetPostTileGeom))); h->d_tgeom = static_cast<bm::DetPostTileGeom*>(p);
-            for (int k = 0; k < 2; ++k) {
-                BM_HIP(hipHostMalloc(&p, ST * sizeof(bm::DetPostTileGeom), hipHostMallocDefault));
-                h->h_tgeom[k] = static_cast<bm::DetPostTileGeom*>(p);
-            }
-            h->tgeom.resize(ST);
-            const int lds = (int)bm::detpost_lds_bytes(c->max_candidates);
-            BM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(bm::k_detpost_select_tiled<float>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            BM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(bm::k_detpost_select_tiled<_Float16>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        } else if (oc) {
-            const int lds = (int)bm::detpost_obb_lds_bytes(c->max_candidates);
-            BM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(bm::k_detpost_select_obb<float>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            BM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(bm::k_detpost_select_obb<_Float16>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+            h->tgeom.create((size_t)c->n_streams * tc->n_tiles);
+            detpost_allow_lds(bm::k_detpost_select_tiled<float>, bm::k_detpost_select_tiled<_Float16>, bm::detpost_lds_bytes(c->max_candidates));
         } else {
-            const int lds = (int)bm::detpost_lds_bytes(c->max_candidates);
-            BM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(bm::k_detpost_select<float>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            BM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(bm::k_detpost_select<_Float16>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+            h->geom.create((size_t)c->n_streams);
+            if (oc) detpost_allow_lds(bm::k_detpost_select_obb<float>, bm::k_detpost_select_obb<_Float16>, bm::detpost_obb_lds_bytes(c->max_candidates));
+            else detpost_allow_lds(bm::k_detpost_select<float>, bm::k_detpost_select<_Float16>, bm::detpost_lds_bytes(c->max_candidates));
         }
     });
     if (!ok) { const std::string e = g_last_error; destroy_on(h); g_last_error = e; return nullptr; }
@@ -3200,19 +3254,9 @@ void boxmot_hip_detpost_destroy(BoxMOTHipDetPost* handle) { destroy_on(handle); 
 int boxmot_hip_detpost_run(BoxMOTHipDetPost* handle, int n_streams, const void* d_pred, int dtype, const double* geom, float* d_dets,
                            int out_stride_rows, int* d_det_rows, void* hip_stream) {
     return guard_on(handle, [&]() {
-        if (!handle) throw std::runtime_error("boxmot_hip: null detpost handle");
+        detpost_check_run(handle, false, n_streams, d_pred, dtype, geom, d_dets, out_stride_rows, d_det_rows);
         const BoxMOTHipDetPostConfig& c = handle->cfg;
-        if (handle->n_tiles) throw std::runtime_error("boxmot_hip: a tiled detpost handle is run with boxmot_hip_detpost_run_tiled");
-        if (n_streams < 1 || n_streams > c.n_streams)
-            throw std::runtime_error("boxmot_hip: detpost stream count " + std::to_string(n_streams) + " out of range for a handle of " + std::to_string(c.n_streams));
-        if (!d_pred || !geom || !d_dets || !d_det_rows) throw std::runtime_error("boxmot_hip: null detpost argument");
-        if (dtype != 0 && dtype != 1) throw std::runtime_error("boxmot_hip: unknown detpost dtype " + std::to_string(dtype) + " (0 fp32, 1 fp16)");
-        if ((uintptr_t)d_pred % (dtype ? 2 : 4) || (uintptr_t)d_dets % 4 || (uintptr_t)d_det_rows % 4)
-            throw std::runtime_error("boxmot_hip: detpost device addresses must be aligned to their element size");
-        if (out_stride_rows < c.max_det)
-            throw std::runtime_error("boxmot_hip: detpost out_stride_rows " + std::to_string(out_stride_rows) + " is below max_det " + std::to_string(c.max_det));
         std::vector<bm::DetPostGeom> g(n_streams);
-        bool same = n_streams <= handle->geom_valid;
         for (int s = 0; s < n_streams; ++s) {
             const double* v = geom + 5 * s;
             if (!(v[0] > 0.0) || !std::isfinite(v[0]) || !(v[3] >= 1.0) || !(v[4] >= 1.0) || !std::isfinite(v[1]) || !std::isfinite(v[2]) ||
@@ -3220,28 +3264,11 @@ int boxmot_hip_detpost_run(BoxMOTHipDetPost* handle, int n_streams, const void* 
                 throw std::runtime_error("boxmot_hip: detpost stream " + std::to_string(s) + ": geometry needs gain > 0 and a frame of >= 1 x 1 (gain " +
                                          std::to_string(v[0]) + ", rows " + std::to_string(v[3]) + ", cols " + std::to_string(v[4]) + ")");
             g[s] = bm::DetPostGeom{(float)v[0], (float)v[1], (float)v[2], (float)v[3], (float)v[4]};
-            if (same && std::memcmp(&g[s], &handle->geom[s], sizeof(bm::DetPostGeom)) != 0) same = false;
         }
-        hipStream_t st = static_cast<hipStream_t>(hip_stream);
-        if (handle->ran) BM_HIP(hipStreamWaitEvent(st, handle->done, 0));      // the scratch and the table are the handle's
-        if (!same) {
-            const int k = handle->geom_uploads & 1;
-            if (handle->geom_uploads >= 2) BM_HIP(hipEventSynchronize(handle->geom_copied[k]));    // (two uploads ago: long done)
-            std::memcpy(handle->h_geom[k], g.data(), n_streams * sizeof(bm::DetPostGeom));
-            BM_HIP(hipMemcpyAsync(handle->d_geom, handle->h_geom[k], n_streams * sizeof(bm::DetPostGeom), hipMemcpyHostToDevice, st));
-            BM_HIP(hipEventRecord(handle->geom_copied[k], st));
-            handle->geom_uploads += 1;
-            std::copy(g.begin(), g.end(), handle->geom.begin());
-            if (handle->geom_valid < n_streams) handle->geom_valid = n_streams;
-        }
-        bm::DetPostArgs a{d_pred, handle->d_geom, handle->d_allow, handle->d_keys, handle->d_cls, d_dets, d_det_rows, handle->d_counters,
-                          c.n_anchors, c.n_classes, c.layout, c.max_candidates, c.max_det, c.agnostic ? 1 : 0, out_stride_rows, c.conf_thres, c.iou_thres,
-                          handle->obb, handle->nms_mode, handle->regularize};
-        DetPostLaunch launch{st};
-        bm::detpost_launch(launch, a, n_streams, dtype);
-        BM_HIP(hipGetLastError());
-        BM_HIP(hipEventRecord(handle->done, st));
-        handle->ran = true;
+        const bm::DetPostArgs a{d_pred, handle->geom.d, handle->d_allow, handle->d_keys, handle->d_cls, d_dets, d_det_rows, handle->d_counters,
+                                c.n_anchors, c.n_classes, c.layout, c.max_candidates, c.max_det, c.agnostic ? 1 : 0, out_stride_rows, c.conf_thres,
+                                c.iou_thres, handle->obb, handle->nms_mode, handle->regularize};
+        detpost_run(handle, handle->geom, g, n_streams, hip_stream, [&](DetPostLaunch& on) { bm::detpost_launch(on, a, n_streams, dtype); });
     });
 }
 
@@ -3253,22 +3280,11 @@ BoxMOTHipDetPost* boxmot_hip_detpost_create_tiled(const BoxMOTHipDetPostTiledCon
 int boxmot_hip_detpost_run_tiled(BoxMOTHipDetPost* handle, int n_streams, const void* d_pred, int dtype, const double* geom, float* d_dets,
                                  int out_stride_rows, int* d_det_rows, void* hip_stream) {
     return guard_on(handle, [&]() {
-        if (!handle) throw std::runtime_error("boxmot_hip: null detpost handle");
+        detpost_check_run(handle, true, n_streams, d_pred, dtype, geom, d_dets, out_stride_rows, d_det_rows);
         const BoxMOTHipDetPostConfig& c = handle->cfg;
-        if (!handle->n_tiles) throw std::runtime_error("boxmot_hip: boxmot_hip_detpost_run_tiled needs a handle of boxmot_hip_detpost_create_tiled");
-        if (n_streams < 1 || n_streams > c.n_streams)
-            throw std::runtime_error("boxmot_hip: detpost stream count " + std::to_string(n_streams) + " out of range for a handle of " + std::to_string(c.n_streams));
-        if (!d_pred || !geom || !d_dets || !d_det_rows) throw std::runtime_error("boxmot_hip: null detpost argument");
-        if (dtype != 0 && dtype != 1) throw std::runtime_error("boxmot_hip: unknown detpost dtype " + std::to_string(dtype) + " (0 fp32, 1 fp16)");
-        if ((uintptr_t)d_pred % (dtype ? 2 : 4) || (uintptr_t)d_dets % 4 || (uintptr_t)d_det_rows % 4)
-            throw std::runtime_error("boxmot_hip: detpost device addresses must be aligned to their element size");
-        if (out_stride_rows < c.max_det)
-            throw std::runtime_error("boxmot_hip: detpost out_stride_rows " + std::to_string(out_stride_rows) + " is below max_det " + std::to_string(c.max_det));
         const int T = handle->n_tiles;
-        const size_t n = (size_t)n_streams * T;
-        std::vector<bm::DetPostTileGeom> g(n);
-        bool same = n_streams <= handle->geom_valid;
-        for (size_t k = 0; k < n; ++k) {
+        std::vector<bm::DetPostTileGeom> g((size_t)n_streams * T);
+        for (size_t k = 0; k < g.size(); ++k) {
             const double* v = geom + 7 * k;
             bool finite = true;
             for (int q = 0; q < 7; ++q) finite = finite && std::isfinite(v[q]);
@@ -3277,29 +3293,12 @@ int boxmot_hip_detpost_run_tiled(BoxMOTHipDetPost* handle, int n_streams, const 
                                          ": geometry needs finite values, gain > 0 and a tile of >= 1 x 1 (gain " + std::to_string(v[0]) + ", w " +
                                          std::to_string(v[5]) + ", h " + std::to_string(v[6]) + ")");
             g[k] = bm::DetPostTileGeom{(float)v[0], (float)v[1], (float)v[2], (float)v[3], (float)v[4], (float)v[5], (float)v[6]};
-            if (same && std::memcmp(&g[k], &handle->tgeom[k], sizeof(bm::DetPostTileGeom)) != 0) same = false;
         }
-        hipStream_t st = static_cast<hipStream_t>(hip_stream);
-        if (handle->ran) BM_HIP(hipStreamWaitEvent(st, handle->done, 0));      // the scratch and the table are the handle's
-        if (!same) {
-            const int k = handle->geom_uploads & 1;
-            if (handle->geom_uploads >= 2) BM_HIP(hipEventSynchronize(handle->geom_copied[k]));    // (two uploads ago: long done)
-            std::memcpy(handle->h_tgeom[k], g.data(), n * sizeof(bm::DetPostTileGeom));
-            BM_HIP(hipMemcpyAsync(handle->d_tgeom, handle->h_tgeom[k], n * sizeof(bm::DetPostTileGeom), hipMemcpyHostToDevice, st));
-            BM_HIP(hipEventRecord(handle->geom_copied[k], st));
-            handle->geom_uploads += 1;
-            std::copy(g.begin(), g.end(), handle->tgeom.begin());
-            if (handle->geom_valid < n_streams) handle->geom_valid = n_streams;
-        }
-        bm::DetPostTiledArgs a{bm::DetPostArgs{d_pred, nullptr, handle->d_allow, handle->d_keys, handle->d_cls, d_dets, d_det_rows, handle->d_counters,
-                                               c.n_anchors, c.n_classes, c.layout, c.max_candidates, c.max_det, c.agnostic ? 1 : 0, out_stride_rows,
-                                               c.conf_thres, c.iou_thres, 0, 0, 0},
-                               handle->d_tgeom, T, handle->merge};
-        DetPostLaunch launch{st};
-        bm::detpost_launch_tiled(launch, a, n_streams, dtype);
-        BM_HIP(hipGetLastError());
-        BM_HIP(hipEventRecord(handle->done, st));
-        handle->ran = true;
+        const bm::DetPostTiledArgs a{bm::DetPostArgs{d_pred, nullptr, handle->d_allow, handle->d_keys, handle->d_cls, d_dets, d_det_rows, handle->d_counters,
+                                                     c.n_anchors, c.n_classes, c.layout, c.max_candidates, c.max_det, c.agnostic ? 1 : 0, out_stride_rows,
+                                                     c.conf_thres, c.iou_thres, 0, 0, 0},
+                                     handle->tgeom.d, T, handle->merge};
+        detpost_run(handle, handle->tgeom, g, n_streams, hip_stream, [&](DetPostLaunch& on) { bm::detpost_launch_tiled(on, a, n_streams, dtype); });
     });
 }
 

@@ -56,13 +56,10 @@
 //          anchors and the lowest ranks fill what is left -- so nothing depends on arrival order;
 //       c. a bitonic sort, descending, of the next power of two >= the candidate count (padding words are 0, below every key);
 //       d. box decode from pred into LDS;
-//       e. NMS in chunks of 64.  The 64 x 64 "j would suppress l" matrix of the chunk is made by all eight wavefronts at once, a
-//          ballot per row (every IoU division of the chunk runs in parallel; rows of candidates the earlier chunks suppressed are
-//          skipped); the greedy pass itself is then one step on 64-bit masks per kept candidate, which every wavefront makes for
-//          itself; wavefront 0 emits the kept rows (rank = kept so far + the kept lanes below) and all wavefronts apply the chunk's
-//          kept boxes to the later candidates.  Two workgroup barriers per chunk, none per
-//          candidate.  The loop does not stop at max_det kept: counter 2 is the count BEFORE the cut and needs every chunk.
-//          (Measured: resolving a chunk with one wavefront, 64 dependent steps of ballot + IoU, took 12 us per chunk.)
+//       e. NMS in chunks of 64 and the rows: the chunk's 64 x 64 matrix, a ballot per row; the greedy pass on bit masks; the rows;
+//          the carry-over to the later chunks.  The stage is explained once, above dp_finish; the oriented kernel and the tiled
+//          one of det_post_tiled.hpp have the same stage written out with their record, their "j suppresses i" and their row.
+//          dp_finish then writes d_det_rows and the counters (all three kernels).
 //   No floating-point atomic anywhere.  LDS: 8 + 16 + 4 + 1 bytes per candidate slot (K rounded up to a power of two) + 1.6 KB:
 //   31 KB at the default K = 1024, 118 KB at K = 4096, of the 160 KB of a CU.
 #pragma once
@@ -354,43 +351,76 @@ __device__ inline DpCount dp_select_sort(const DetPostArgs& g, int s, const DpLd
     return DpCount{n_pass, n_cand};
 }
 
+__device__ inline float dp_readlane_f32(float v, int l) { return __uint_as_float(BM_READLANE_U32(__float_as_uint(v), l)); }
+// a candidate's record out of lane l's registers (v_readlane with a wave-uniform lane)
+__device__ inline DpBox dp_readlane(const DpBox& b, int l) {
+    return DpBox{dp_readlane_f32(b.x1, l), dp_readlane_f32(b.y1, l), dp_readlane_f32(b.x2, l), dp_readlane_f32(b.y2, l)};
+}
+
+// Stage e of the three select kernels (this one, k_detpost_select_obb, k_detpost_select_tiled) is the NMS over the sorted
+// candidates, in chunks of 64, and the rows of the kept ones.  It is explained here once; each kernel has it WRITTEN OUT with its
+// own record (DpBox, or the oriented kernel's DpGauss), its own "j suppresses i" and its own row, so a fix to the stage has to be
+// made in all three.  (Tried: one function template for the whole stage, and one for everything after the matrix rows.  Any
+// function boundary inside the chunk loop changes the code the compiler makes of it, and the kernels measured 0.3 - 5 % slower,
+// outside the parent's run-to-run spread: profiles/frontend_refactor_ab.txt.)  Per chunk:
+//   1. the chunk's 64 x 64 matrix, with all eight wavefronts at once: lane l of every wavefront holds candidate c0 + l (`mine`,
+//      `mcls`), wavefront w makes the rows j = 8 w .. 8 w + 7 -- bit l of row j: "j, if kept, suppresses l" (l > j only, and only
+//      for the l the earlier chunks left alive, `live0`: the others are dropped whatever the row says) -- one ballot per row into
+//      rowm, so every division of the chunk runs in parallel; a workgroup barrier follows.  (Measured: resolving a chunk with one
+//      wavefront, 64 dependent steps of ballot + IoU, took 12 us per chunk.)
+//   2. every wavefront works out the chunk's survivors `km` for itself, so no barrier stands between that and what follows.
+//      greedy: one step on 64-bit masks per KEPT candidate, lane l holding row l (the rows of candidates the earlier chunks
+//      dropped are empty).  fast (the oriented kernel in nms_mode 1 only): rowm[w] is the OR of wavefront w's eight rows and the
+//      survivors are the live lanes outside the OR of all of them.
+//   3. wavefront 0 emits: row `rank` = kept so far + the kept lanes below, for the first max_det kept.
+//   4. all wavefronts apply the chunk's kept candidates -- fast: ALL its candidates (the chunk is full when there is a later
+//      one) -- to the candidates of the later chunks, classes compared here; a second barrier closes the chunk.
+// Two workgroup barriers per chunk, none per candidate.  The loop does not stop at max_det kept: counter 2 is the count BEFORE
+// the cut and needs every chunk.
+
+// the row count and the counters of stream s (steps 5 and 6)
+__device__ inline void dp_finish(const DetPostArgs& g, int s, const DpCount& cnt, int kept) {
+    if (threadIdx.x != 0) return;
+    g.det_rows[s] = kept < g.max_det ? kept : g.max_det;
+    g.counters[s * DP_COUNTERS + 0] = cnt.n_pass;
+    g.counters[s * DP_COUNTERS + 1] = cnt.n_cand;
+    g.counters[s * DP_COUNTERS + 2] = kept;
+}
+
 template <class T>
 __global__ void __launch_bounds__(DP_THREADS) k_detpost_select(DetPostArgs g) {
     BM_DYNAMIC_LDS_T(unsigned char, lds);
     const int slots = detpost_slots(g.K);
     const DpLds m = dp_lds(lds, slots, (int)sizeof(DpBox));
-    unsigned long long* cand = m.cand;
+    const unsigned long long* cand = m.cand;
     DpBox* box = reinterpret_cast<DpBox*>(m.tab);
-    int* ccls = m.ccls;
-    unsigned long long* rowm = m.rowm;
-    unsigned char* sup = m.sup;
 
-    const int s = (int)blockIdx.x, t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int A = g.A;
+    const int s = (int)blockIdx.x, t = (int)threadIdx.x;
     const T* pred = static_cast<const T*>(g.pred);
-    const unsigned long long below = (1ull << lane) - 1ull;
 
     // a-c. the passing count, the exact top-K, the sort
     const DpCount cnt = dp_select_sort(g, s, m, slots);
-    const int n_pass = cnt.n_pass, n_cand = cnt.n_cand;
 
     // d. boxes
-    for (int i = t; i < n_cand; i += DP_THREADS) {
+    for (int i = t; i < cnt.n_cand; i += DP_THREADS) {
         const int a = (int)(0xffffffffu - (uint32_t)cand[i]);
         const float cx = dp_load(pred, dp_at(g, s, a, 0)), cy = dp_load(pred, dp_at(g, s, a, 1)), w = dp_load(pred, dp_at(g, s, a, 2)),
                     h = dp_load(pred, dp_at(g, s, a, 3));
         box[i] = DpBox{cx - w * 0.5f, cy - h * 0.5f, cx + w * 0.5f, cy + h * 0.5f};
-        ccls[i] = g.cls[(long)s * A + a];
+        m.ccls[i] = g.cls[(long)s * g.A + a];
     }
     __syncthreads();
 
-    // e. NMS and the rows
+    // e. NMS and the rows, through to_frame's arithmetic (the stage is explained above dp_finish)
     const DetPostGeom geo = g.geom[s];
     float* rows = g.dets + (long)s * g.out_stride * 6;
+    const int n_cand = cnt.n_cand, lane = t & 63, wave = t >> 6;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int* ccls = m.ccls;
+    unsigned long long* rowm = m.rowm;
+    unsigned char* sup = m.sup;
     int kept = 0;                   // (the same in every thread)
     for (int c0 = 0; c0 < n_cand; c0 += DP_CHUNK) {
-        // the chunk's 64 x 64 suppression matrix, in parallel: lane l of every wavefront holds candidate c0 + l, wavefront w makes
-        // the rows j = 8 w .. 8 w + 7 -- bit l of row j: "j, if kept, suppresses l" (l > j only) -- one ballot per row
         const int i = c0 + lane;
         const bool valid = i < n_cand;
         const DpBox mine = valid ? box[i] : DpBox{0.f, 0.f, 0.f, 0.f};
@@ -402,17 +432,13 @@ __global__ void __launch_bounds__(DP_THREADS) k_detpost_select(DetPostArgs g) {
                 if (lane == 0) rowm[j] = 0ull;
                 continue;
             }
-            // candidate j's box and class out of lane j's registers (v_readlane with a uniform lane)
-            const DpBox bj{__uint_as_float(BM_READLANE_U32(__float_as_uint(mine.x1), j)), __uint_as_float(BM_READLANE_U32(__float_as_uint(mine.y1), j)),
-                           __uint_as_float(BM_READLANE_U32(__float_as_uint(mine.x2), j)), __uint_as_float(BM_READLANE_U32(__float_as_uint(mine.y2), j))};
+            const DpBox bj = dp_readlane(mine, j);                          // candidate j's box and class out of lane j's registers
             const int cj = (int)BM_READLANE_U32((unsigned)mcls, j);
             const bool hit = ((live0 >> lane) & 1ull) && lane > j && (g.agnostic || cj == mcls) && dp_suppresses(bj, mine, g.iou_thres);
-            const unsigned long long m = __ballot(hit);
-            if (lane == 0) rowm[j] = m;
+            const unsigned long long hm = __ballot(hit);
+            if (lane == 0) rowm[j] = hm;
         }
         __syncthreads();
-        // the greedy pass over the chunk, on bit masks: one step per KEPT candidate; every wavefront makes it for itself (no barrier
-        // before the next part), lane l holding row l
         const unsigned long long myrow = rowm[lane];
         const unsigned mylo = (unsigned)myrow, myhi = (unsigned)(myrow >> 32);
         unsigned long long km = live0;
@@ -440,20 +466,15 @@ __global__ void __launch_bounds__(DP_THREADS) k_detpost_select(DetPostArgs g) {
                 if (sup[q]) continue;
                 const DpBox qb = box[q];
                 const int qcls = ccls[q];
-                for (unsigned long long m = km; m; m &= m - 1ull) {
-                    const int j = c0 + __builtin_ctzll(m);
+                for (unsigned long long mm = km; mm; mm &= mm - 1ull) {
+                    const int j = c0 + __builtin_ctzll(mm);
                     if ((g.agnostic || ccls[j] == qcls) && dp_suppresses(box[j], qb, g.iou_thres)) { sup[q] = 1; break; }
                 }
             }
         }
         __syncthreads();
     }
-    if (t == 0) {
-        g.det_rows[s] = kept < g.max_det ? kept : g.max_det;
-        g.counters[s * DP_COUNTERS + 0] = n_pass;
-        g.counters[s * DP_COUNTERS + 1] = n_cand;
-        g.counters[s * DP_COUNTERS + 2] = kept;
-    }
+    dp_finish(g, s, cnt, kept);
 }
 
 }  // namespace bm
@@ -462,22 +483,32 @@ __global__ void __launch_bounds__(DP_THREADS) k_detpost_select(DetPostArgs g) {
 
 namespace bm {
 
-// The kernel sequence of one call (L: the library's stream launcher, or the test harness's CPU-thread launcher).
+// The score kernel of a call over n_tensors prediction tensors (L: the library's stream launcher, or the test harness's CPU-thread
+// launcher): wide where the layout, the anchor count and the tensor's alignment allow it.
 template <class L>
-inline void detpost_launch(L& launch, const DetPostArgs& g, int n_streams, int fp16, size_t* lds_bytes = nullptr) {
-    const size_t lds = g.obb ? detpost_obb_lds_bytes(g.K) : detpost_lds_bytes(g.K);
-    if (lds_bytes) *lds_bytes = lds;
+inline void detpost_launch_score(L& launch, const DetPostArgs& g, int n_tensors, int fp16) {
     const int vec = fp16 ? DpVec<_Float16>::N : DpVec<float>::N;
     const bool wide = g.layout == 0 && g.A % vec == 0 && (uintptr_t)g.pred % 16 == 0;
     const int wide_grid = (g.A / vec + DP_SCORE_VEC_THREADS - 1) / DP_SCORE_VEC_THREADS;
     if (fp16) {
-        if (wide) launch(k_detpost_score_cn_vec<_Float16>, wide_grid, n_streams, DP_SCORE_VEC_THREADS, (size_t)0, g);
-        else launch(k_detpost_score<_Float16>, detpost_score_grid_x(g.A), n_streams, DP_SCORE_THREADS, (size_t)0, g);
+        if (wide) launch(k_detpost_score_cn_vec<_Float16>, wide_grid, n_tensors, DP_SCORE_VEC_THREADS, (size_t)0, g);
+        else launch(k_detpost_score<_Float16>, detpost_score_grid_x(g.A), n_tensors, DP_SCORE_THREADS, (size_t)0, g);
+    } else {
+        if (wide) launch(k_detpost_score_cn_vec<float>, wide_grid, n_tensors, DP_SCORE_VEC_THREADS, (size_t)0, g);
+        else launch(k_detpost_score<float>, detpost_score_grid_x(g.A), n_tensors, DP_SCORE_THREADS, (size_t)0, g);
+    }
+}
+
+// The kernel sequence of one call.
+template <class L>
+inline void detpost_launch(L& launch, const DetPostArgs& g, int n_streams, int fp16, size_t* lds_bytes = nullptr) {
+    const size_t lds = g.obb ? detpost_obb_lds_bytes(g.K) : detpost_lds_bytes(g.K);
+    if (lds_bytes) *lds_bytes = lds;
+    detpost_launch_score(launch, g, n_streams, fp16);
+    if (fp16) {
         if (g.obb) launch(k_detpost_select_obb<_Float16>, n_streams, 1, DP_THREADS, lds, g);
         else launch(k_detpost_select<_Float16>, n_streams, 1, DP_THREADS, lds, g);
     } else {
-        if (wide) launch(k_detpost_score_cn_vec<float>, wide_grid, n_streams, DP_SCORE_VEC_THREADS, (size_t)0, g);
-        else launch(k_detpost_score<float>, detpost_score_grid_x(g.A), n_streams, DP_SCORE_THREADS, (size_t)0, g);
         if (g.obb) launch(k_detpost_select_obb<float>, n_streams, 1, DP_THREADS, lds, g);
         else launch(k_detpost_select<float>, n_streams, 1, DP_THREADS, lds, g);
     }

@@ -47,12 +47,10 @@
 //   k_detpost_select_obb<T>  one workgroup of DP_THREADS per stream; stages a-c are dp_select_sort of det_post.hpp, shared with the
 //       axis-aligned kernel.
 //       d. per candidate (cx, cy, A, B, C), 20 bytes, and its class into LDS: cosf / sinf run once per candidate, not per pair;
-//       e. the chunk structure of k_detpost_select: all eight wavefronts make the chunk's 64 x 64 "j suppresses l" matrix, a ballot
-//          per row, two workgroup barriers per chunk.  greedy: rows of candidates the earlier chunks dropped are skipped, the pass
-//          over the chunk is one step on 64-bit masks per kept candidate, and the chunk's KEPT candidates are applied to the later
-//          ones.  fast: no row of a candidate is skipped for being dropped; every wavefront ORs its eight rows, the chunk's
-//          survivors are the live lanes outside the OR of all rows, and ALL the chunk's candidates are applied to the later ones.
-//          Wavefront 0 emits; it reloads w, h and the angle of the kept anchors from pred.
+//       e. the chunked 64 x 64 ballot NMS explained in det_post.hpp, written out here with DpGauss as the record,
+//          dp_suppresses_obb as the predicate and both modes (fast: no row is skipped for being dropped, every wavefront ORs its
+//          eight rows, and all of a chunk's candidates go on to the later chunks).  Wavefront 0 emits; it reloads w, h and the
+//          angle of the kept anchors from pred.
 //   No floating-point atomic.  LDS: 8 + 20 + 4 + 1 bytes per candidate slot + 1.6 KB: 35 KB at K = 1024, 137 KB at K = 4096.
 #pragma once
 
@@ -81,7 +79,9 @@ __device__ inline bool dp_suppresses_obb(const DpGauss& p, const DpGauss& q, flo
     return iou >= thres;
 }
 
-__device__ inline float dp_readlane_f32(float v, int l) { return __uint_as_float(BM_READLANE_U32(__float_as_uint(v), l)); }
+__device__ inline DpGauss dp_readlane(const DpGauss& g, int l) {
+    return DpGauss{dp_readlane_f32(g.x, l), dp_readlane_f32(g.y, l), dp_readlane_f32(g.a, l), dp_readlane_f32(g.b, l), dp_readlane_f32(g.c, l)};
+}
 
 template <class T>
 __global__ void __launch_bounds__(DP_THREADS) k_detpost_select_obb(DetPostArgs g) {
@@ -103,7 +103,7 @@ __global__ void __launch_bounds__(DP_THREADS) k_detpost_select_obb(DetPostArgs g
 
     // a-c. the passing count, the exact top-K, the sort
     const DpCount cnt = dp_select_sort(g, s, m, slots);
-    const int n_pass = cnt.n_pass, n_cand = cnt.n_cand;
+    const int n_cand = cnt.n_cand;
 
     // d. Gaussians
     for (int i = t; i < n_cand; i += DP_THREADS) {
@@ -114,7 +114,8 @@ __global__ void __launch_bounds__(DP_THREADS) k_detpost_select_obb(DetPostArgs g
     }
     __syncthreads();
 
-    // e. NMS and the rows
+    // e. NMS and the rows, in both modes: the stage that is explained above k_detpost_select (det_post.hpp), written out with this
+    // kernel's record, predicate and row.  w, h and the angle of a kept anchor are reloaded from pred.
     const DetPostGeom geo = g.geom[s];
     float* rows = g.dets + (long)s * g.out_stride * 7;
     int kept = 0;                   // (the same in every thread)
@@ -135,8 +136,7 @@ __global__ void __launch_bounds__(DP_THREADS) k_detpost_select_obb(DetPostArgs g
                 if (!fast && lane == 0) rowm[j] = 0ull;
                 continue;
             }
-            const DpGauss gj{dp_readlane_f32(mine.x, j), dp_readlane_f32(mine.y, j), dp_readlane_f32(mine.a, j), dp_readlane_f32(mine.b, j),
-                             dp_readlane_f32(mine.c, j)};
+            const DpGauss gj = dp_readlane(mine, j);
             const int cj = (int)BM_READLANE_U32((unsigned)mcls, j);
             const bool hit = ((live0 >> lane) & 1ull) && lane > j && (g.agnostic || cj == mcls) && dp_suppresses_obb(gj, mine, g.iou_thres);
             const unsigned long long mj = __ballot(hit);
@@ -198,12 +198,7 @@ __global__ void __launch_bounds__(DP_THREADS) k_detpost_select_obb(DetPostArgs g
         }
         __syncthreads();
     }
-    if (t == 0) {
-        g.det_rows[s] = kept < g.max_det ? kept : g.max_det;
-        g.counters[s * DP_COUNTERS + 0] = n_pass;
-        g.counters[s * DP_COUNTERS + 1] = n_cand;
-        g.counters[s * DP_COUNTERS + 2] = kept;
-    }
+    dp_finish(g, s, cnt, kept);
 }
 
 }  // namespace bm

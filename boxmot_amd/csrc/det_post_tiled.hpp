@@ -23,8 +23,9 @@
 // Ultralytics is not pinned by any test.)
 //
 // k_detpost_select_tiled<T>: one workgroup of DP_THREADS per stream.  Stages a-c are dp_select_sort, stage d decodes and maps to the
-// frame, stage e is the chunked 64 x 64 ballot NMS of k_detpost_select with the metric selected (a wave-uniform branch); the LDS
-// layout and the K <= 4096 budget are k_detpost_select's.  The handle's key and class scratch is sized [S * T][A].
+// frame, stage e is the chunked 64 x 64 ballot NMS explained in det_post.hpp, written out here with the metric selected inside
+// this kernel's predicate (a wave-uniform branch); the LDS layout and the K <= 4096 budget are k_detpost_select's.  The handle's
+// key and class scratch is sized [S * T][A].
 #pragma once
 
 #include "det_post.hpp"
@@ -58,25 +59,20 @@ __global__ void __launch_bounds__(DP_THREADS) k_detpost_select_tiled(DetPostTile
     const DetPostArgs& g = ta.base;
     const int slots = detpost_slots(g.K);
     const DpLds m = dp_lds(lds, slots, (int)sizeof(DpBox));
-    unsigned long long* cand = m.cand;
+    const unsigned long long* cand = m.cand;
     DpBox* box = reinterpret_cast<DpBox*>(m.tab);
-    int* ccls = m.ccls;
-    unsigned long long* rowm = m.rowm;
-    unsigned char* sup = m.sup;
 
-    const int s = (int)blockIdx.x, t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int s = (int)blockIdx.x, t = (int)threadIdx.x;
     const int A = g.A, NT = ta.T, merge = ta.merge;
     const T* pred = static_cast<const T*>(g.pred);
-    const unsigned long long below = (1ull << lane) - 1ull;
 
     // a-c. over the stream's T * A keys: the passing count, the exact top-K, the sort (conf descending, t * A + a ascending)
     DetPostArgs all = g;
     all.A = NT * A;
     const DpCount cnt = dp_select_sort(all, s, m, slots);
-    const int n_pass = cnt.n_pass, n_cand = cnt.n_cand;
 
     // d. boxes, in frame coordinates
-    for (int i = t; i < n_cand; i += DP_THREADS) {
+    for (int i = t; i < cnt.n_cand; i += DP_THREADS) {
         const int idx = (int)(0xffffffffu - (uint32_t)cand[i]);
         const int tile = idx / A, a = idx - tile * A, ps = s * NT + tile;
         const float cx = dp_load(pred, dp_at(g, ps, a, 0)), cy = dp_load(pred, dp_at(g, ps, a, 1)), w = dp_load(pred, dp_at(g, ps, a, 2)),
@@ -84,12 +80,17 @@ __global__ void __launch_bounds__(DP_THREADS) k_detpost_select_tiled(DetPostTile
         const DetPostTileGeom q = ta.tgeom[ps];
         box[i] = DpBox{dp_tile_to_frame(cx - w * 0.5f, q.left, q.gain, q.w, q.x0), dp_tile_to_frame(cy - h * 0.5f, q.top, q.gain, q.h, q.y0),
                        dp_tile_to_frame(cx + w * 0.5f, q.left, q.gain, q.w, q.x0), dp_tile_to_frame(cy + h * 0.5f, q.top, q.gain, q.h, q.y0)};
-        ccls[i] = g.cls[(long)s * NT * A + idx];
+        m.ccls[i] = g.cls[(long)s * NT * A + idx];
     }
     __syncthreads();
 
-    // e. NMS and the rows: k_detpost_select's stage e with the metric selected
+    // e. NMS with the metric selected, and the rows as they are: the stage that is explained above k_detpost_select (det_post.hpp)
     float* rows = g.dets + (long)s * g.out_stride * 6;
+    const int n_cand = cnt.n_cand, lane = t & 63, wave = t >> 6;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int* ccls = m.ccls;
+    unsigned long long* rowm = m.rowm;
+    unsigned char* sup = m.sup;
     int kept = 0;                   // (the same in every thread)
     for (int c0 = 0; c0 < n_cand; c0 += DP_CHUNK) {
         const int i = c0 + lane;
@@ -103,15 +104,13 @@ __global__ void __launch_bounds__(DP_THREADS) k_detpost_select_tiled(DetPostTile
                 if (lane == 0) rowm[j] = 0ull;
                 continue;
             }
-            const DpBox bj{__uint_as_float(BM_READLANE_U32(__float_as_uint(mine.x1), j)), __uint_as_float(BM_READLANE_U32(__float_as_uint(mine.y1), j)),
-                           __uint_as_float(BM_READLANE_U32(__float_as_uint(mine.x2), j)), __uint_as_float(BM_READLANE_U32(__float_as_uint(mine.y2), j))};
+            const DpBox bj = dp_readlane(mine, j);
             const int cj = (int)BM_READLANE_U32((unsigned)mcls, j);
             const bool hit = ((live0 >> lane) & 1ull) && lane > j && (g.agnostic || cj == mcls) && dp_merge_suppresses(bj, mine, g.iou_thres, merge);
             const unsigned long long hm = __ballot(hit);
             if (lane == 0) rowm[j] = hm;
         }
         __syncthreads();
-        // the greedy pass over the chunk, on bit masks: one step per KEPT candidate; every wavefront makes it for itself
         const unsigned long long myrow = rowm[lane];
         const unsigned mylo = (unsigned)myrow, myhi = (unsigned)(myrow >> 32);
         unsigned long long km = live0;
@@ -144,34 +143,18 @@ __global__ void __launch_bounds__(DP_THREADS) k_detpost_select_tiled(DetPostTile
         }
         __syncthreads();
     }
-    if (t == 0) {
-        g.det_rows[s] = kept < g.max_det ? kept : g.max_det;
-        g.counters[s * DP_COUNTERS + 0] = n_pass;
-        g.counters[s * DP_COUNTERS + 1] = n_cand;
-        g.counters[s * DP_COUNTERS + 2] = kept;
-    }
+    dp_finish(g, s, cnt, kept);
 }
 
-// The kernel sequence of one tiled call (L as detpost_launch's): the score kernels over the S * T tile tensors, then one select
+// The kernel sequence of one tiled call (L as detpost_launch's): the score kernel over the S * T tile tensors, then one select
 // workgroup per stream.
 template <class L>
 inline void detpost_launch_tiled(L& launch, const DetPostTiledArgs& ta, int n_streams, int fp16, size_t* lds_bytes = nullptr) {
-    const DetPostArgs& g = ta.base;
-    const size_t lds = detpost_lds_bytes(g.K);
+    const size_t lds = detpost_lds_bytes(ta.base.K);
     if (lds_bytes) *lds_bytes = lds;
-    const int vec = fp16 ? DpVec<_Float16>::N : DpVec<float>::N;
-    const bool wide = g.layout == 0 && g.A % vec == 0 && (uintptr_t)g.pred % 16 == 0;
-    const int wide_grid = (g.A / vec + DP_SCORE_VEC_THREADS - 1) / DP_SCORE_VEC_THREADS;
-    const int n_tensors = n_streams * ta.T;
-    if (fp16) {
-        if (wide) launch(k_detpost_score_cn_vec<_Float16>, wide_grid, n_tensors, DP_SCORE_VEC_THREADS, (size_t)0, g);
-        else launch(k_detpost_score<_Float16>, detpost_score_grid_x(g.A), n_tensors, DP_SCORE_THREADS, (size_t)0, g);
-        launch(k_detpost_select_tiled<_Float16>, n_streams, 1, DP_THREADS, lds, ta);
-    } else {
-        if (wide) launch(k_detpost_score_cn_vec<float>, wide_grid, n_tensors, DP_SCORE_VEC_THREADS, (size_t)0, g);
-        else launch(k_detpost_score<float>, detpost_score_grid_x(g.A), n_tensors, DP_SCORE_THREADS, (size_t)0, g);
-        launch(k_detpost_select_tiled<float>, n_streams, 1, DP_THREADS, lds, ta);
-    }
+    detpost_launch_score(launch, ta.base, n_streams * ta.T, fp16);
+    if (fp16) launch(k_detpost_select_tiled<_Float16>, n_streams, 1, DP_THREADS, lds, ta);
+    else launch(k_detpost_select_tiled<float>, n_streams, 1, DP_THREADS, lds, ta);
 }
 
 }  // namespace bm

@@ -118,12 +118,13 @@ __device__ inline void letterbox_row_taps(const BM_GLOBAL uint8_t* row, int xa, 
 
 // 8 neighbouring columns, from x0, of the picture row yy (0 <= yy < new_h) as B | G << 8 | R << 16 each; columns outside the
 // picture are pad3.  PATH is the path of the resize, picked once per stream by the caller -- 0 copy, 1 exact 2 x box filter,
-// 2 bilinear -- so that the 8 pixels are straight-line code: all tap loads are issued before the first is needed.
+// 2 bilinear -- so that the 8 pixels are straight-line code: all tap loads are issued before the first is needed.  The picture's
+// rows lie `stride` bytes apart (a rectangle of a larger frame: ingest_letterbox_tiles.hpp); g.cols bounds the taps, not the stride.
 // resize_sample_f picks its path by comparing the picture's size with the output's; it is told the path with the smallest sizes
 // that select it: 1 -> 1 (copy), 2 -> 1 (box filter), 2 -> 3 (bilinear).
 template <int PATH, bool WIDE>
-__device__ inline void letterbox_row8(const BM_GLOBAL uint8_t* src, const LetterboxGeom& g, int yy, int x0, uint32_t pad3, uint32_t (&u)[LB_PX]) {
-    const long stride = (long)g.cols * 3;
+__device__ inline void letterbox_row8(const BM_GLOBAL uint8_t* src, long stride, const LetterboxGeom& g, int yy, int x0, uint32_t pad3,
+                                      uint32_t (&u)[LB_PX]) {
     ResizeAxis ay{0, 0, 0, 0};
     if (PATH == 2) ay = resize_axis_y(yy, g.new_h, g.rows);
     const int ya = PATH == 0 ? yy : (PATH == 1 ? 2 * yy : ay.s0), yb = PATH == 0 ? yy : (PATH == 1 ? 2 * yy + 1 : ay.s1);
@@ -148,19 +149,17 @@ __device__ inline void letterbox_row8(const BM_GLOBAL uint8_t* src, const Letter
     }
 }
 
-// lut: the 256 entries of T as bit patterns, one 32-bit word each (fp32: the float's bits; fp16: the half's bits in the low 16).
-// out: (gridDim.y, 3, H, W) of 2-byte (fp16 != 0) or 4-byte elements, 16-byte aligned; W % 8 == 0.
-__global__ void __launch_bounds__(LB_THREADS) k_letterbox(const uint8_t* const* __restrict__ frames, const LetterboxGeom* __restrict__ geom,
-                                                          const uint32_t* __restrict__ lut, void* __restrict__ out, int H, int W, int fp16,
-                                                          int rgb, int pad) {
-    const int s = (int)blockIdx.y;
+// What one thread of the two letterbox kernels does: its 8 columns of one row of output tensor `tensor`, all three planes, from the
+// picture at src with rows `stride` bytes apart and the geometry g.  blockIdx.x and threadIdx.x name the item (8 columns of one
+// row each, row-major).  lut: the 256 entries of T as bit patterns, one 32-bit word each (fp32: the float's bits; fp16: the half's
+// bits in the low 16).  out: (tensors, 3, H, W) of 2-byte (fp16 != 0) or 4-byte elements, 16-byte aligned; W % 8 == 0.
+__device__ inline void letterbox_item(const BM_GLOBAL uint8_t* src, long stride, const LetterboxGeom& g, int tensor, const uint32_t* __restrict__ lut,
+                                      void* __restrict__ out, int H, int W, int fp16, int rgb, int pad) {
     const int tcols = W / LB_PX;
-    const long item = (long)blockIdx.x * LB_THREADS + (long)threadIdx.x;       // 8 columns of one row each, row-major
+    const long item = (long)blockIdx.x * LB_THREADS + (long)threadIdx.x;
     if (item >= (long)H * tcols) return;
     const int y = (int)(item / tcols), x0 = (int)(item - (long)y * tcols) * LB_PX;
-    const LetterboxGeom g = geom[s];
-    const BM_GLOBAL uint8_t* src = (const BM_GLOBAL uint8_t*)frames[s];
-    const bool same = g.cols == g.new_w && g.rows == g.new_h, half = g.cols == 2 * g.new_w && g.rows == 2 * g.new_h;     // (per stream)
+    const bool same = g.cols == g.new_w && g.rows == g.new_h, half = g.cols == 2 * g.new_w && g.rows == 2 * g.new_h;     // (per picture)
     const uint32_t pad3 = (uint32_t)pad * 0x010101u;
 
     uint32_t u[LB_PX];                  // B | G << 8 | R << 16 of this thread's 8 columns of the letterboxed picture
@@ -169,12 +168,12 @@ __global__ void __launch_bounds__(LB_THREADS) k_letterbox(const uint8_t* const* 
 #pragma unroll
         for (int k = 0; k < LB_PX; ++k) u[k] = pad3;
     } else if (g.cols >= 2) {
-        if (same) letterbox_row8<0, true>(src, g, yy, x0, pad3, u);
-        else if (half) letterbox_row8<1, true>(src, g, yy, x0, pad3, u);
-        else letterbox_row8<2, true>(src, g, yy, x0, pad3, u);
-    } else {                            // a one-column frame (never an exact 2 x: that needs an even width)
-        if (same) letterbox_row8<0, false>(src, g, yy, x0, pad3, u);
-        else letterbox_row8<2, false>(src, g, yy, x0, pad3, u);
+        if (same) letterbox_row8<0, true>(src, stride, g, yy, x0, pad3, u);
+        else if (half) letterbox_row8<1, true>(src, stride, g, yy, x0, pad3, u);
+        else letterbox_row8<2, true>(src, stride, g, yy, x0, pad3, u);
+    } else {                            // a one-column picture (never an exact 2 x: that needs an even width)
+        if (same) letterbox_row8<0, false>(src, stride, g, yy, x0, pad3, u);
+        else letterbox_row8<2, false>(src, stride, g, yy, x0, pad3, u);
     }
     uint32_t v[3][LB_PX];               // the table entries per output plane
 #pragma unroll
@@ -188,7 +187,7 @@ __global__ void __launch_bounds__(LB_THREADS) k_letterbox(const uint8_t* const* 
     const long plane = (long)H * W, at = (long)y * W + x0;
 #pragma unroll
     for (int p = 0; p < 3; ++p) {
-        const long e = ((long)s * 3 + p) * plane + at;                 // element index: a multiple of 8
+        const long e = ((long)tensor * 3 + p) * plane + at;            // element index: a multiple of 8
         if (fp16) {
             lb_u32x4 w;
 #pragma unroll
@@ -202,6 +201,16 @@ __global__ void __launch_bounds__(LB_THREADS) k_letterbox(const uint8_t* const* 
             o[0] = w0; o[1] = w1;
         }
     }
+}
+
+// frames: the slot's [gridDim.y] frame pointers, geom: [gridDim.y]; lut, out, H, W, fp16, rgb, pad as letterbox_item's, out being
+// (gridDim.y, 3, H, W).
+__global__ void __launch_bounds__(LB_THREADS) k_letterbox(const uint8_t* const* __restrict__ frames, const LetterboxGeom* __restrict__ geom,
+                                                          const uint32_t* __restrict__ lut, void* __restrict__ out, int H, int W, int fp16,
+                                                          int rgb, int pad) {
+    const int s = (int)blockIdx.y;
+    const LetterboxGeom g = geom[s];
+    letterbox_item((const BM_GLOBAL uint8_t*)frames[s], (long)g.cols * 3, g, s, lut, out, H, W, fp16, rgb, pad);
 }
 
 }  // namespace bm

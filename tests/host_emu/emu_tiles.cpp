@@ -3,25 +3,14 @@
 //   n_streams * n_tiles, LB_THREADS threads) and the geometry the library computes (bm::letterbox_tile_geometry).  It has no barrier
 //   and no cross-lane operation: the emulated threads of a workgroup run one after the other, the workgroups on a few OS threads;
 //   the tiled post-processing (boxmot_amd/csrc/det_post_tiled.hpp) through its kernel sequence detpost_launch_tiled.
-//   k_detpost_select_tiled has workgroup barriers, ballots and LDS atomics, so its workgroups run on the barrier-capable emulation
-//   of hip_shim.hpp (fibers; pthreads under the sanitizers).  The scratch and the dynamic LDS are filled with a poison byte before
-//   every call.
-#include "hip_shim.hpp"
-
-#include <cstdlib>
-#include <functional>
-#include <vector>
+//   k_detpost_select_tiled has workgroup barriers, ballots and LDS atomics, so its workgroups run on emu_detpost.cpp's launcher,
+//   included as emu_detpost_obb.cpp includes it: the barrier-capable emulation of hip_shim.hpp (fibers; pthreads under the
+//   sanitizers), the dynamic LDS poisoned before every workgroup.  The scratch is poisoned before every call.
+#include "emu_detpost.cpp"
 
 #define BM_GLOBAL
 #include "../../boxmot_amd/csrc/ingest_letterbox_tiles.hpp"
 #include "../../boxmot_amd/csrc/det_post_tiled.hpp"
-
-thread_local EmuDim3 threadIdx;
-thread_local EmuDim3 blockIdx;
-EmuDim3 blockDim;
-EmuDim3 gridDim;
-EmuBlock* g_emu_block = nullptr;
-unsigned char* g_emu_dynamic_lds = nullptr;
 
 namespace {
 struct Job {
@@ -39,35 +28,6 @@ void* worker(void* p) {
     }
     return nullptr;
 }
-
-struct TA { const std::function<void()>* fn; int tid, bx, by; };
-void* tmain(void* p) {
-    TA* a = static_cast<TA*>(p);
-    threadIdx.x = a->tid; blockIdx.x = a->bx; blockIdx.y = a->by;
-    (*a->fn)();
-    return nullptr;
-}
-struct Launcher {
-    template <class K, class... A>
-    void operator()(K kernel, int gx, int gy, int nthr, size_t lds_bytes, A... args) {
-        const std::function<void()> fn = [=]() { kernel(args...); };
-        static EmuBlock block;
-        g_emu_block = &block;
-        blockDim.x = nthr; gridDim.x = gx; gridDim.y = gy;
-        std::vector<unsigned char> lds(lds_bytes + 16);         // exactly what the launch asks for: a sanitizer sees an overrun
-        g_emu_dynamic_lds = lds.data();
-        for (int by = 0; by < gy; ++by)
-            for (int bx = 0; bx < gx; ++bx) {
-                block.block_barrier.init(nthr);
-                for (int w = 0; w < EMU_MAX_WAVES; ++w) block.wave_barrier[w].init(EMU_WAVE);
-                std::memset(lds.data(), 0xCD, lds_bytes);
-                std::vector<TA> ta(nthr);
-                for (int t = 0; t < nthr; ++t) ta[t] = TA{&fn, t, bx, by};
-                emu_run_threads(nthr, tmain, ta.data(), sizeof(ta[0]), 1 << 18);
-            }
-        g_emu_dynamic_lds = nullptr;
-    }
-};
 }  // namespace
 
 // the library's geometry of one rectangle: out5 = gain, new_w, new_h, top, left; returns 1, 0 where the picture would vanish, -1

@@ -37,3 +37,11 @@ def test_hot_kernels_keep_their_register_budget():
         assert v["vgpr"] <= 128, (k, v)                                     # 16 waves = 4 per SIMD
     for k, v in find("k_gemm_f16_glds").items():
         assert v["scratch"] == 0, (k, v)
+    # the detection front-end: the two letterbox kernels share their body (letterbox_item) and the three select
+    # kernels, fp16 and fp32 each, their helpers; what the sharing must not cost is registers -- the counts of the separate copies
+    for sub, n, vgpr in (("k_letterboxE", 1, 48), ("k_letterbox_tilesE", 1, 48), ("k_detpost_selectI", 2, 42), ("k_detpost_select_obbI", 2, 78),
+                         ("k_detpost_select_tiledI", 2, 36)):
+        front = find(sub)
+        assert len(front) == n, (sub, sorted(front))
+        for k, v in front.items():
+            assert v["vgpr"] <= vgpr and v["scratch"] == 0 and v["spill"] == 0, (k, v)

@@ -19,7 +19,7 @@ import letterbox_tiles_ref as lref
 
 HERE = Path(__file__).resolve().parent / "host_emu"
 CSRC = HERE.parent.parent / "boxmot_amd" / "csrc"
-DEPS = [HERE / "emu_tiles.cpp", HERE / "hip_shim.hpp"] + [CSRC / n for n in ("ingest_letterbox_tiles.hpp", "ingest_letterbox.hpp", "reid_kernels_v1.hpp",
+DEPS = [HERE / "emu_tiles.cpp", HERE / "emu_detpost.cpp", HERE / "hip_shim.hpp"] + [CSRC / n for n in ("ingest_letterbox_tiles.hpp", "ingest_letterbox.hpp", "reid_kernels_v1.hpp",
                                                                              "reid_layout.hpp", "det_post_tiled.hpp", "det_post.hpp", "det_post_obb.hpp",
                                                                              "kernel_macros.hpp")]
 CXX = shutil.which("clang++", path="/opt/rocm/lib/llvm/bin") or shutil.which("clang++") or "g++"       # (a compiler with _Float16)
