@@ -1,4 +1,4 @@
-// TEST-ONLY plumbing shared by the known-answer harnesses (gemm_kat.hip, clip_kat.hip, reid_hp_kat.hip, wide_kat.hip): the device build's launch / copy helpers and, with
+// TEST-ONLY plumbing shared by the known-answer harnesses (gemm_kat.hip, clip_kat.hip, reid_hp_kat.hip, wide_kat.hip, wide_hp_kat.hip): the device build's launch / copy helpers and, with
 // -DKAT_EMU, their CPU-thread twins over tests/host_emu/hip_shim.hpp (one workgroup after the other, LDS poisoned before each).  Include it
 // FIRST and once per harness: it defines the emulation's globals, so every harness is a single translation unit.
 //   KAT_LAUNCH(kernel, grid, block, dynamic LDS bytes, args...)    KAT_SET_LDS(kernel, bytes): hipFuncSetAttribute once per instantiation
