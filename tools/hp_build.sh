@@ -2,6 +2,7 @@
 # Build one variant of tools/hp_prof (the fp32-grade x0.25 kernels' launch-time profiler) in its own directory and print the register /
 # spill / scratch table of its k_osblock_hp instantiations (from the saved ISA):
 #   tools/hp_build.sh <name> [-D<switch>=<v> ...]        -> tools/_build/hp_prof_<name>  (picked up by `tools/gpu_session.sh <tag> hpab`)
+# <switch>: BM_HP_NBR_SYNC, BM_HP_DW_PREFETCH, BM_HP_PERSIST or BM_HP_S0_RECOMP (the block at the top of reid_hp.hpp)
 set -u
 R=$(cd "$(dirname "$0")/.." && pwd)
 N=$1; shift

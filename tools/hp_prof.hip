@@ -1,6 +1,7 @@
 // Standalone launch-time / phase profiler for the fp32-grade fused ReID kernels (reid_hp.hpp).  Development tool, not part of the library.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off [-DBM_OSBLOCK_PROF] [-D<variant switches>] -I boxmot_amd/csrc \
 //         tools/hp_prof.hip -o tools/_build/hp_prof[_variant] && tools/_build/hp_prof [n_crops] [iters]
+// Variant switches (the block at the top of reid_hp.hpp): BM_HP_NBR_SYNC, BM_HP_DW_PREFETCH, BM_HP_PERSIST, BM_HP_S0_RECOMP.
 // Random weights and activations (only the access pattern and the instruction stream matter); prints the best launch time of every
 // kernel of the family and, in a -DBM_OSBLOCK_PROF build, the shader-clock cycles per wave of each phase of k_osblock_hp.
 #include <hip/hip_runtime.h>
