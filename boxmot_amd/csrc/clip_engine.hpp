@@ -16,11 +16,6 @@
 #include "clip_kernels.hpp"
 #include "reid_pack.hpp"
 
-// A/B switches (tools/clip_bench.py with BOXMOT_HIP_LIB pointing at a variant build)
-#ifndef BM_CLIP_ATTN_T
-#define BM_CLIP_ATTN_T 1
-#endif
-
 namespace bm {
 
 constexpr int CLIP_MAGIC = 0x434C5031;       // "CLP1"
@@ -92,7 +87,7 @@ public:
         for (const ClipLayerOff& l : L_) {
             layernorm(d_w_ + l.ln1_w, d_w_ + l.ln1_b, R, st);
             gemm<0>(h16_, d_w16_ + l.qkv_w, d_w_ + l.qkv_b, qkv16_, R, 3 * D, D, st);
-            if (BM_CLIP_ATTN_T && T == 129)        // ViT-B/16 on 256 x 128 crops: the compile-time-T kernel (identical bits, tools/attn_prof.hip)
+            if (T == 129)        // ViT-B/16 on 256 x 128 crops: the compile-time-T kernel (identical bits, tools/attn_prof.hip; 192 -> 134 us, profiles/r6_clip_ab.txt)
                 hipLaunchKernelGGL((k_clip_attention_t<129>), dim3((unsigned)(n * heads)), dim3(192), (size_t)clip_attn_t_lds_bytes<129>(), st,
                                    qkv16_, h16_, D, heads);
             else

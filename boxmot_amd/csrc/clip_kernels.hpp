@@ -264,15 +264,13 @@ typedef short cs4 __attribute__((ext_vector_type(4)));
 #define BM_DS_READ_TR16_B64(lds_ptr) \
     __builtin_bit_cast(ch4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) cs4*)(lds_ptr)))
 #endif
-#ifndef BM_CLIP_ATTN_QB
-#define BM_CLIP_ATTN_QB 1          // query tiles a wave runs together: 1 = three passes at 112 registers, three workgroups per CU (0.112 ms per layer at 512 crops);
-                                   // 3 = every K / V fragment read feeds three MFMAs but 240 registers, two workgroups per CU (0.134 ms) -- profiles/r6_clip_ab.txt
-#endif
 constexpr int ATT_VLD = 80;             // halves per V row in LDS: 8 consecutive keys land on disjoint 8-bank windows (40 dwords apart)
 template <int T>
 __host__ __device__ constexpr int clip_attn_t_lds_bytes() { return (((T + 15) / 16 * 16) * ATT_LD + ((T + 31) / 32 * 32) * ATT_VLD) * 2; }
 
-template <int T, int QB = BM_CLIP_ATTN_QB>
+// QB = query tiles a wave runs together: 1 = three passes at 112 registers, three workgroups per CU (0.112 ms per layer at 512 crops);
+// 3 = every K / V fragment read feeds three MFMAs but 240 registers, two workgroups per CU (0.134 ms) -- profiles/r6_clip_ab.txt
+template <int T, int QB = 1>
 __global__ void __launch_bounds__(192) k_clip_attention_t(const _Float16* __restrict__ qkv, _Float16* __restrict__ out, int D, int heads) {
     constexpr int TP = (T + 15) / 16 * 16, NKT = TP / 16, KP = (T + 31) / 32 * 32, NKS = KP / 32, NQ = NKT / 3;
     static_assert(NKT % 3 == 0 && T <= ATT_MAX_T && NQ % QB == 0, "three waves share the query tiles evenly, QB of them per pass");

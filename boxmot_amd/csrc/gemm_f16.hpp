@@ -385,9 +385,6 @@ __global__ void __launch_bounds__(256) k_gemm_f16_glds(const _Float16* __restric
 constexpr int GEMM256_EPI_LD = 136;                        // halves per row of a wave's epilogue region (128 + 8 of padding)
 constexpr int GEMM256_LDS_BYTES = 8 * 64 * GEMM256_EPI_LD * 2;       // 136 KB: the epilogue regions; the k-loop uses 2 x 4 half tiles = 128 KB of it
 
-#ifndef BM_GEMM_EPI2_DEEP
-#define BM_GEMM_EPI2_DEEP 1
-#endif
 #ifndef BM_GEMM_PHASE_SYNC
 #define BM_GEMM_PHASE_SYNC() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 #define BM_GEMM_BARRIER() asm volatile("s_barrier" ::: "memory")
@@ -521,9 +518,6 @@ __global__ void __launch_bounds__(512) k_gemm_f16_256(const _Float16* __restrict
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
                 cf4 v = acc[p][t];
-#ifdef BM_GEMM256_NO_STORE
-                if (v[0] != 12345.678f) continue;            // profiling build: the main loop alone
-#endif
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] += bv[r];
                 if constexpr (EPI == 1) {    // QuickGELU; the quotient as a reciprocal (1 ulp of fp32, the result is rounded to fp16): the IEEE
@@ -550,7 +544,6 @@ __global__ void __launch_bounds__(512) k_gemm_f16_256(const _Float16* __restrict
             }
         }
         BM_WAVE_LDS_SYNC();
-#ifndef BM_GEMM256_NO_STORE
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             const int row = i * 4 + g;
@@ -558,30 +551,28 @@ __global__ void __launch_bounds__(512) k_gemm_f16_256(const _Float16* __restrict
             const ch8 v = *reinterpret_cast<const ch8*>(reg + row * GEMM256_EPI_LD + l16 * 8);
             if (m < M) *reinterpret_cast<ch8*>(static_cast<_Float16*>(Cout) + m * N + n0 + wr * 128 + l16 * 8) = v;
         }
-#endif
         return;
     }
     if constexpr (EPI == 2) {
         // fp32 C += result, the same way in two halves of 64 features: 4 rows x 256 contiguous bytes per load / store instruction
         // instead of 16-byte pieces of 16 rows (the residual stream is read and rewritten once per projection: 2 x 101 MB at 256 crops).
-        // BM_GEMM_EPI2_DEEP: the sixteen loads of a half's old values are all requested BEFORE the half's accumulators go through LDS
-        // (the fragment registers are dead: 64 more fit), so a half waits for HBM once instead of twice and the wait runs under the
-        // transposition; 0: two batches of eight, each requested and waited for at its use.
+        // The sixteen loads of a half's old values are all requested BEFORE the half's accumulators go through LDS (the fragment
+        // registers are dead: 64 more fit), so a half waits for HBM once instead of twice and the wait runs under the transposition:
+        // -2.5 ... -4 % against two batches of eight, each requested and waited for at its use (profiles/r6_clip_ab.txt).
         float* reg = reinterpret_cast<float*>(lds_raw) + wave * (64 * 68);
         float* c = static_cast<float*>(Cout);
-        constexpr int NB = BM_GEMM_EPI2_DEEP ? 16 : 8;          // loads in flight
 #pragma unroll
         for (int hp = 0; hp < 2; ++hp) {
-            cf4 old[NB];
-            auto request = [&](int i0) {
+            cf4 old[16];
+            auto request = [&]() {          // (a lambda on purpose: written straight into the loop the kernel's registers are allocated differently)
 #pragma unroll
-                for (int i = 0; i < NB; ++i) {
-                    long m = m0 + wc * 64 + (i0 + i) * 4 + g;
+                for (int i = 0; i < 16; ++i) {
+                    long m = m0 + wc * 64 + i * 4 + g;
                     if (m >= M) m = M - 1;
                     old[i] = *reinterpret_cast<const cf4*>(c + m * N + n0 + wr * 128 + hp * 64 + l16 * 4);
                 }
             };
-            if constexpr (BM_GEMM_EPI2_DEEP) request(0);
+            request();
 #pragma unroll
             for (int pp = 0; pp < 4; ++pp) {
                 const int p = hp * 4 + pp, n = n0 + wr * 128 + p * 16 + 4 * g;
@@ -600,19 +591,13 @@ __global__ void __launch_bounds__(512) k_gemm_f16_256(const _Float16* __restrict
             }
             BM_WAVE_LDS_SYNC();
 #pragma unroll
-            for (int i0 = 0; i0 < 16; i0 += NB) {
-                if constexpr (!BM_GEMM_EPI2_DEEP) request(i0);
+            for (int i = 0; i < 16; ++i) {
+                const int row = i * 4 + g;
+                const long m = m0 + wc * 64 + row;
+                const cf4 v = *reinterpret_cast<const cf4*>(reg + row * 68 + l16 * 4);
 #pragma unroll
-                for (int i = 0; i < NB; ++i) {
-                    const int row = (i0 + i) * 4 + g;
-                    const long m = m0 + wc * 64 + row;
-                    const cf4 v = *reinterpret_cast<const cf4*>(reg + row * 68 + l16 * 4);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) old[i][r] += v[r];
-#ifndef BM_GEMM256_NO_STORE
-                    if (m < M) *reinterpret_cast<cf4*>(c + m * N + n0 + wr * 128 + hp * 64 + l16 * 4) = old[i];
-#endif
-                }
+                for (int r = 0; r < 4; ++r) old[i][r] += v[r];
+                if (m < M) *reinterpret_cast<cf4*>(c + m * N + n0 + wr * 128 + hp * 64 + l16 * 4) = old[i];
             }
             BM_WAVE_LDS_SYNC();
         }
@@ -630,9 +615,6 @@ __global__ void __launch_bounds__(512) k_gemm_f16_256(const _Float16* __restrict
         for (int t = 0; t < 4; ++t) {
             const long m = m0 + wc * 64 + t * 16 + l16;
             if (m >= M) continue;
-#ifdef BM_GEMM256_NO_STORE
-            if (acc[p][t][0] != 12345.678f) continue;        // profiling build: the main loop alone
-#endif
             cf4 v = acc[p][t];
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[r] += bv[r];

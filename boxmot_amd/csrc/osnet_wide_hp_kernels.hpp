@@ -385,15 +385,14 @@ __device__ unsigned long long g_chain_prof[8];
 #define BM_CPROF(k) ((void)0)
 #define BM_CPROF_FLUSH() ((void)0)
 #endif
-#ifndef BM_CHAIN_TGP
-#define BM_CHAIN_TGP 2              // tiles whose B operands are resident while the A pairs stream by (A/B switch)
-#endif
 
 template <int C, int W, int WR, int HALO>
 struct ChainGeo {
     static constexpr int CT = C / 16, KS = C / 32, R = WR - 2 * HALO;
     static constexpr int NW = 8, NTILES = WR * W / 16, NT = NTILES / NW;
-    static constexpr int TGP = NT % BM_CHAIN_TGP == 0 ? BM_CHAIN_TGP : 1;                 // tiles whose B operands are resident while the A pairs stream by
+    // tiles whose B operands are resident while the A pairs stream by: 2 where NT is even (16.35 ms per 1024 crops against 17.38 with 1
+    // and 17.07 with 3, profiles/r4_c3_chain_phase_clocks_v1.txt)
+    static constexpr int TGP = NT % 2 == 0 ? 2 : 1;
     static constexpr int ROWP = (W + 2) * 16;
     static constexpr int PLANE = ((WR + 2) * ROWP + 255) / 256 * 256;
     static constexpr int SLICE = 4 * PLANE;

@@ -27,10 +27,9 @@
 
 namespace bm {
 
-#ifndef BM_WIDE_BAND
-#define BM_WIDE_BAND 8
-#endif
-constexpr int WIDE_BAND = BM_WIDE_BAND;       // image rows per k_light_fused workgroup (8 or 4: must divide the smallest image height, 16)
+// image rows per k_light_fused workgroup (must divide the smallest image height, 16); a 4-row band -- more workgroups per CU, 1.5x
+// the halo reads -- measured 19 % slower (docs/history/DESIGN_rounds_1-5.md, the wide-OSNet LightConv variants)
+constexpr int WIDE_BAND = 8;
 
 // widths this kernel family takes: GEMM k-steps of 32, 16-channel MFMA tiles, k_light_fused's thread mapping
 inline bool wide_osnet_supports(const OsnetLayout& L) {

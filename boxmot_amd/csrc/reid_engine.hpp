@@ -25,13 +25,6 @@
 #include "osnet_wide.hpp"
 #include "osnet_wide_hp.hpp"
 
-#ifndef BM_STAGE1_HANDOVER
-#define BM_STAGE1_HANDOVER 0
-#endif
-#ifndef BM_HEAD_PER_CROP
-#define BM_HEAD_PER_CROP 0          // 1: the round-1 head (one workgroup of two waves per crop) instead of k_head_batched
-#endif
-
 // default of BOXMOT_HIP_REID_PERSIST (the fp32-grade x0.25 block kernels as persistent workgroups; A/B: profiles/r5_hp_persist_ab.txt)
 #ifndef BM_HP_PERSIST_DEFAULT
 #define BM_HP_PERSIST_DEFAULT 0
@@ -504,7 +497,7 @@ private:
             BlkLink{w_blk_[0], bp_[0].conv3_a, bp_[0].conv3_b, bp_[0].down_a, x2s_});
 #if BM_STAGE1_HANDOVER
         // the same hand-over for stage 1 (its 512 x 96 block output is otherwise written once and read twice); validated in
-        // emulation (tests/test_reid_emu.py), not yet measured on the device -- off by default
+        // emulation (tests/test_reid_emu.py), measured a 0.2 % gain on the device (BM_STAGE1_HANDOVER, reid_fused.hpp) -- off by default
         blk(k_osblock<1, 64, true, false, true, false>, Geo<1>::NWAVES, Geo<1>::LDS_BYTES, act_b_, nullptr, 2, nullptr,
             BlkLink{w_blk_[3], bp_[3].conv1_a, bp_[3].conv1_b, 0, x2s_});
         blk(k_osblock<1, 96, false, true, false, true>, Geo<1>::NWAVES, Geo<1>::LDS_BYTES, act_b_, act_a_, 3, w_tr_[1],
@@ -517,12 +510,8 @@ private:
 #endif
         blk(k_osblock<2, 96, true, false>, Geo<2>::NWAVES, Geo<2>::LDS_BYTES, s2_in, s2_mid, 4, nullptr, BlkLink{});
         blk(k_osblock<2, 128, false, false>, Geo<2>::NWAVES, Geo<2>::LDS_BYTES, s2_mid, s2_in, 5, nullptr, BlkLink{});
-#if BM_HEAD_PER_CROP
-        hipLaunchKernelGGL((k_head_fused<128, 512>), dim3(n), dim3(128), 0, st, s2_in, w_c5_, w_fc_, d_out, d_out_rows, d_count_);
-#else
         hipLaunchKernelGGL((k_head_batched<128, 512>), dim3((n + HEAD_NB - 1) / HEAD_NB), dim3(256), HeadGeo<128>::LDS_BYTES, st, s2_in,
                            w_c5_, w_fc_, d_out, d_out_rows, d_count_, n);
-#endif
     }
     // ---- fused fp32-grade path (OSNet-x0.25, mode 2): reid_hp.hpp ----
     void prepare_hp() {

@@ -24,41 +24,30 @@
 #include "reid_kernels_v1.hpp"
 #include "reid_pack.hpp"
 
+// The switches of this file and of the fused part of reid_engine.hpp that stay selectable.
+// Stage 1 as an EMIT / RECON block pair like stage 0 (1; reid_engine.hpp forward_fused): its 512 x 96 block output is otherwise
+// written once and read twice.  tests/test_reid_emu.py runs both values on the CPU emulation, tools/osblock_prof.hip times the pair;
+// measured on the device as a 0.2 % gain (docs/history/DESIGN_rounds_1-5.md, the round-2 variants), too little to ship: off.
+#ifndef BM_STAGE1_HANDOVER
+#define BM_STAGE1_HANDOVER 0
+#endif
+// In-kernel phase clocks of k_osblock for tools/osblock_prof.hip (never defined in the product build)
+#ifdef BM_OSBLOCK_PROF
+namespace bm { __device__ unsigned long long g_osblock_prof[8]; }
+#define BM_PROF_DECL() unsigned long long prof_t = clock64(), prof_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}
+#define BM_PROF(k) do { unsigned long long t_ = clock64(); prof_acc[k] += t_ - prof_t; prof_t = t_; } while (0)
+#define BM_PROF_FLUSH() do { if ((threadIdx.x & 63) == 0) for (int k_ = 0; k_ < 8; ++k_) atomicAdd(&g_osblock_prof[k_], prof_acc[k_]); } while (0)
+#else
+#define BM_PROF_DECL() ((void)0)
+#define BM_PROF(k) ((void)0)
+#define BM_PROF_FLUSH() ((void)0)
+#endif
+
 namespace bm {
 
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef float f4 __attribute__((ext_vector_type(4)));
-
-// Unmeasured variants for the next round (validated in emulation, off by default): epilogue operands of the stage-2
-// blocks through LDS as in stages 0-1, and a <= 128-VGPR build of them (4 instead of 3 workgroups per CU).
-#ifndef BM_STAGE2_EPI_LDS
-#define BM_STAGE2_EPI_LDS 0
-#endif
-#ifndef BM_STAGE2_OCC4
-#define BM_STAGE2_OCC4 0
-#endif
-// Memory-latency hiding in the OSBlock kernels (bit-identical results), measured per kernel at 4096 crops
-// (tools/osblock_prof.hip, profiles/r2_osblock_variants.txt):
-//   BM_PREFETCH_CONV1: conv1 issues all of its input loads before its first MFMA             -> -1.7 % over the six kernels
-//   BM_PREFETCH_EPI:   the epilogue loads tile i + 1's operands (block input for the shortcut / downsample, the hand-over
-//                      tensors) while tile i computes: -6 % on the stage-1 second block, but +3 % / +7 % on the stage-0 RECON
-//                      and stage-2 first blocks (they are at the 128-register budget: the second operand set spills), so it
-//                      is compiled in for that one kernel only (value 2 = "where it pays"; 0 / 1 = off / everywhere for A/B).
-#ifndef BM_PREFETCH_CONV1
-#define BM_PREFETCH_CONV1 1
-#endif
-#ifndef BM_PREFETCH_EPI
-#define BM_PREFETCH_EPI 2
-#endif
-
-// Stage-0 LightConv3x3 as ONE dense 3x3 on the matrix pipe (reid_pack.hpp pack_light_dense): no LDS image, no depthwise
-// VALU loop -- per 16-pixel tile 3 K=32 + 3 K=16 MFMAs on pixel-shifted copies of the rows (DPP row shifts inside a tile, the
-// neighbour tile's edge pixel by a row rotate), rows of other waves through a 2 x 16 KiB LDS halo exchange (one barrier per
-// layer).  0 = the round-1 layer (1x1 MFMA -> LDS image -> sliding-window depthwise on packed-fp16 FMAs).
-#ifndef BM_DENSE_LIGHT
-#define BM_DENSE_LIGHT 0
-#endif
 
 template <int STAGE>
 struct Geo {
@@ -76,15 +65,13 @@ struct Geo {
     static constexpr int NT = P / 16 / NWAVES;              // 16, 4, 2 pixel tiles per wave
     static constexpr bool SWZ = STAGE == 0;
     static constexpr bool RECOMP = STAGE == 0;
-    static constexpr int WG_PER_CU_WAVES = (STAGE == 2 && !BM_STAGE2_OCC4) ? 1 : 4;     // __launch_bounds__ 2nd argument (waves per SIMD)
+    // __launch_bounds__ 2nd argument (waves per SIMD); a <= 128-VGPR build of stage 2 (4 instead of 3 workgroups per CU) gained
+    // 1 % together with LDS-staged epilogue operands (docs/history/DESIGN_rounds_1-5.md, the round-2 variants) and was not kept
+    static constexpr int WG_PER_CU_WAVES = STAGE == 2 ? 1 : 4;
     static constexpr int PXB = SWZ ? 32 : (KT == 1 ? 40 : 72);      // bytes per pixel of the LDS image
     static constexpr int ROWB = (W + 2) * PXB;
     static constexpr int IMG = (H + 2) * ROWB;
-    // stage 2 with LDS-staged epilogue operands: conv3 (8 KiB) + bias + downsample 96 -> 128 (24 KiB) outgrow the image
-    static constexpr bool DENSE = BM_DENSE_LIGHT && STAGE == 0;
-    static constexpr int HALO = 2 * NWAVES * 2 * 2 * 64 * 8;       // [layer parity][wave][first / last row][half][lane] h4
-    static constexpr int TBUF = DENSE ? HALO : ((STAGE == 2 && BM_STAGE2_EPI_LDS && IMG < 33280) ? 33280 : IMG);
-    static constexpr int LDS_BYTES = TBUF + 4 * NWAVES * HID * 4;          // image + per-branch gate partials
+    static constexpr int LDS_BYTES = IMG + 4 * NWAVES * HID * 4;          // image + per-branch gate partials
 };
 
 // (y, x) of lane l16 in pixel tile q: tiles are 16 consecutive pixels in row-major order
@@ -97,18 +84,6 @@ __device__ inline int tile_lds_offset(int q, int l16) {
     else { y = 2 * q + (l16 >> 3); x = l16 & 7; }
     return (y + 1) * G::ROWB + (x + 1) * G::PXB;
 }
-
-// Optional in-kernel phase clocks for tools/osblock_prof.hip (never defined in the product build)
-#ifdef BM_OSBLOCK_PROF
-__device__ unsigned long long g_osblock_prof[8];
-#define BM_PROF_DECL() unsigned long long prof_t = clock64(), prof_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}
-#define BM_PROF(k) do { unsigned long long t_ = clock64(); prof_acc[k] += t_ - prof_t; prof_t = t_; } while (0)
-#define BM_PROF_FLUSH() do { if ((threadIdx.x & 63) == 0) for (int k_ = 0; k_ < 8; ++k_) atomicAdd(&g_osblock_prof[k_], prof_acc[k_]); } while (0)
-#else
-#define BM_PROF_DECL() ((void)0)
-#define BM_PROF(k) ((void)0)
-#define BM_PROF_FLUSH() ((void)0)
-#endif
 
 __device__ inline h4 to_h4(f4 v) { return h4{(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]}; }
 __device__ inline h4 residual_h4(f4 v, h4 h) { return h4{(_Float16)(v[0] - (float)h[0]), (_Float16)(v[1] - (float)h[1]), (_Float16)(v[2] - (float)h[2]), (_Float16)(v[3] - (float)h[3])}; }
@@ -136,33 +111,6 @@ __device__ inline h8 cat8(h4 a, h4 b) { return h8{a[0], a[1], a[2], a[3], b[0], 
 //     recomputes it per tile from the PREVIOUS block's branch sum and input (`in` is the previous block's input;
 //     conv3 / bias / downsample fragments of the previous block at link.a0 / a1 / a2 of `link.w`).  Same operations
 //     in the same order on the same fp16 values: bit-identical to storing and re-reading the tensor.
-typedef unsigned int u2v __attribute__((ext_vector_type(2)));
-// Value of the pixel to the left (x - 1) / right (x + 1) of every lane's pixel in a 16-pixel row tile, as DPP moves inside the
-// rows of 16 lanes (lane = pixel + 16 * channel group: a row of lanes is one channel group of the tile's 16 pixels).  The
-// tile's outer lane takes the facing edge pixel of the neighbour tile `edge` (row rotate), or zero at the image border.
-template <bool HAS_EDGE>
-__device__ inline h4 pixel_left(h4 c, h4 edge) {
-    const u2v u = __builtin_bit_cast(u2v, c), e = __builtin_bit_cast(u2v, edge);
-    u2v r;
-#pragma unroll
-    for (int d = 0; d < 2; ++d) {
-        if constexpr (HAS_EDGE) r[d] = BM_DPP_U32(BM_DPP_U32(0u, e[d], 0x121, true), u[d], 0x111, false);      // row_ror:1, then row_shr:1 keeping lane 0
-        else r[d] = BM_DPP_U32(0u, u[d], 0x111, true);
-    }
-    return __builtin_bit_cast(h4, r);
-}
-template <bool HAS_EDGE>
-__device__ inline h4 pixel_right(h4 c, h4 edge) {
-    const u2v u = __builtin_bit_cast(u2v, c), e = __builtin_bit_cast(u2v, edge);
-    u2v r;
-#pragma unroll
-    for (int d = 0; d < 2; ++d) {
-        if constexpr (HAS_EDGE) r[d] = BM_DPP_U32(BM_DPP_U32(0u, e[d], 0x12F, true), u[d], 0x101, false);      // row_ror:15, then row_shl:1 keeping lane 15
-        else r[d] = BM_DPP_U32(0u, u[d], 0x101, true);
-    }
-    return __builtin_bit_cast(h4, r);
-}
-
 struct BlkLink {
     const unsigned char* w = nullptr;
     long a0 = 0, a1 = 0, a2 = 0;
@@ -186,7 +134,7 @@ k_osblock(const _Float16* __restrict__ in, _Float16* __restrict__ out, const uns
     constexpr bool STASH = G::RECOMP && CIN != 16 && !RECON;      // conv1 output parked in global scratch (L2-resident re-reads)
     BM_DYNAMIC_LDS_T(unsigned char, lds);
     unsigned char* tbuf = lds;
-    float* gap_part = reinterpret_cast<float*>(lds + G::TBUF);      // [4 branches][NWAVES][HID]
+    float* gap_part = reinterpret_cast<float*>(lds + G::IMG);      // [4 branches][NWAVES][HID]
 
     // (a scalar wave index, as in the stem, was measured here and is 5-15 % slower: more scalar traffic, no VALU saved)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, l16 = lane & 15;
@@ -196,8 +144,7 @@ k_osblock(const _Float16* __restrict__ in, _Float16* __restrict__ out, const uns
     BM_PROF_DECL();
 
     // zero the LDS image once: the halo ring stays zero (= the dw conv's zero padding)
-    if constexpr (!G::DENSE)
-        for (int e = tid * 8; e < G::IMG; e += 64 * G::NWAVES * 8) *reinterpret_cast<unsigned long long*>(tbuf + e) = 0ull;
+    for (int e = tid * 8; e < G::IMG; e += 64 * G::NWAVES * 8) *reinterpret_cast<unsigned long long*>(tbuf + e) = 0ull;
 
     // ---- conv1: 1x1 CIN -> MID, + bias, ReLU (osnet.py:248) ----
     auto conv1_into = [&](h4 (&x1)[NT][KT]) {
@@ -208,9 +155,9 @@ k_osblock(const _Float16* __restrict__ in, _Float16* __restrict__ out, const uns
         for (int ct = 0; ct < KT; ++ct) bias[ct] = *reinterpret_cast<const f4*>(wts + bp.conv1_b + (16 * ct + 4 * g) * 4);
         if constexpr (CIN == 16) {
             const h4 a = *reinterpret_cast<const h4*>(wts + bp.conv1_a + lane * 8);
-#if BM_PREFETCH_CONV1
             // all input loads first, into the registers the results will live in: one memory round trip per call instead
-            // of one per group of four tiles (the phase is latency-bound: 16 waves per CU, 8-byte loads)
+            // of one per group of four tiles (the phase is latency-bound: 16 waves per CU, 8-byte loads); -1.7 % over the six
+            // kernels (profiles/r2_osblock_variants.txt)
 #pragma unroll
             for (int i = 0; i < NT; ++i) {
                 const int p = (wave * NT + i) * 16 + l16;
@@ -219,15 +166,6 @@ k_osblock(const _Float16* __restrict__ in, _Float16* __restrict__ out, const uns
             BM_SCHED_FENCE();
 #pragma unroll
             for (int i = 0; i < NT; ++i) x1[i][0] = relu_h4(to_h4(BM_MFMA_F16_K16(a, x1[i][0], bias[0])));
-#else
-#pragma unroll
-            for (int i = 0; i < NT; ++i) {
-                const int p = (wave * NT + i) * 16 + l16;
-                const h4 b = *reinterpret_cast<const h4*>(xin + (xo + (unsigned)(p * CIN + g * 4)));
-                x1[i][0] = relu_h4(to_h4(BM_MFMA_F16_K16(a, b, bias[0])));
-                if ((i & 3) == 3) BM_SCHED_FENCE();
-            }
-#endif
         } else {
             h8 a[KIN][KT];
 #pragma unroll
@@ -235,7 +173,6 @@ k_osblock(const _Float16* __restrict__ in, _Float16* __restrict__ out, const uns
 #pragma unroll
                 for (int ct = 0; ct < KT; ++ct)
                     a[ks][ct] = *reinterpret_cast<const h8*>(wts + bp.conv1_a + ((ks * KT + ct) * 64 + lane) * 16);
-#if BM_PREFETCH_CONV1
             constexpr int GRP = NT * KIN <= 12 ? NT : 4;        // tiles whose loads are in flight together (<= 48 registers)
 #pragma unroll
             for (int i0 = 0; i0 < NT; i0 += GRP) {
@@ -262,24 +199,6 @@ k_osblock(const _Float16* __restrict__ in, _Float16* __restrict__ out, const uns
                 }
                 BM_SCHED_FENCE();
             }
-#else
-#pragma unroll
-            for (int i = 0; i < NT; ++i) {
-                const int p = (wave * NT + i) * 16 + l16;
-                f4 acc[KT];
-#pragma unroll
-                for (int ct = 0; ct < KT; ++ct) acc[ct] = bias[ct];
-#pragma unroll
-                for (int ks = 0; ks < KIN; ++ks) {
-                    const h8 b = *reinterpret_cast<const h8*>(xin + (xo + (unsigned)(p * CIN + g * (CIN / 4) + 8 * ks)));
-#pragma unroll
-                    for (int ct = 0; ct < KT; ++ct) acc[ct] = BM_MFMA_F16_K32(a[ks][ct], b, acc[ct]);
-                }
-#pragma unroll
-                for (int ct = 0; ct < KT; ++ct) x1[i][ct] = relu_h4(to_h4(acc[ct]));
-                if (i & 1) BM_SCHED_FENCE();
-            }
-#endif
         }
     };
     h4 x1[NT][KT];
@@ -350,66 +269,8 @@ k_osblock(const _Float16* __restrict__ in, _Float16* __restrict__ out, const uns
 #pragma unroll 1
         for (int k = 0; k <= br; ++k, ++li) {
             const unsigned char* lw = wts + bp.light0 + (long)li * bp.light_bytes;
-            if constexpr (G::DENSE) {
-                // ---- LightConv3x3 as a dense 3x3 on the matrix pipe (pack_light_dense) ----
-                static_assert(!G::DENSE || (STAGE == 0 && KT == 1 && NT == 16), "dense LightConv: stage 0 geometry");
-                const unsigned char* ld = wts + bp.dense0 + (long)li * bp.dense_bytes;
-                h8 aP[3];
-                h4 aR[3];
-#pragma unroll
-                for (int dy = 0; dy < 3; ++dy) {
-                    aP[dy] = *reinterpret_cast<const h8*>(ld + dy * 1024 + lane * 16);
-                    aR[dy] = *reinterpret_cast<const h4*>(ld + 3072 + dy * 512 + lane * 8);
-                }
-                const f4 lbias = *reinterpret_cast<const f4*>(lw + bp.light_b + (4 * g) * 4);
-                // rows of the neighbouring waves: every wave publishes its first and last row, one barrier, then reads the row
-                // above its strip (last row of wave - 1) and below it (first row of wave + 1); the two buffers alternate by
-                // layer, so a wave that is one layer ahead never overwrites rows a slower wave still has to read
-                unsigned char* hb = tbuf + (li & 1) * (G::HALO / 2);
-                auto hslot = [&](int w, int which, int hf) { return hb + (((w * 2 + which) * 2 + hf) * 64 + lane) * 8; };
-                *reinterpret_cast<h4*>(hslot(wave, 0, 0)) = cur[0][0];
-                *reinterpret_cast<h4*>(hslot(wave, 0, 1)) = cur[1][0];
-                *reinterpret_cast<h4*>(hslot(wave, 1, 0)) = cur[NT - 2][0];
-                *reinterpret_cast<h4*>(hslot(wave, 1, 1)) = cur[NT - 1][0];
-                BM_PROF(2);
-                __syncthreads();
-                BM_PROF(3);
-                const h4 zero4 = (h4)(_Float16)0.f;
-                h4 up[2] = {zero4, zero4}, dn[2] = {zero4, zero4};
-                if (wave > 0) { up[0] = *reinterpret_cast<const h4*>(hslot(wave - 1, 1, 0)); up[1] = *reinterpret_cast<const h4*>(hslot(wave - 1, 1, 1)); }
-                if (wave < G::NWAVES - 1) { dn[0] = *reinterpret_cast<const h4*>(hslot(wave + 1, 0, 0)); dn[1] = *reinterpret_cast<const h4*>(hslot(wave + 1, 0, 1)); }
-                struct RowOps { h8 P[2]; h4 R[2]; };
-                auto build = [&](h4 c0, h4 c1) {
-                    RowOps o;
-                    o.P[0] = cat8(pixel_left<false>(c0, c0), c0);
-                    o.P[1] = cat8(pixel_left<true>(c1, c0), c1);
-                    o.R[0] = pixel_right<true>(c0, c1);
-                    o.R[1] = pixel_right<false>(c1, c1);
-                    return o;
-                };
-                RowOps w0 = build(up[0], up[1]), w1 = build(cur[0][0], cur[1][0]);
-#pragma unroll
-                for (int r = 0; r < NT / 2; ++r) {
-                    const RowOps w2 = r + 1 < NT / 2 ? build(cur[2 * r + 2][0], cur[2 * r + 3][0]) : build(dn[0], dn[1]);
-#pragma unroll
-                    for (int hf = 0; hf < 2; ++hf) {
-                        f4 accP = lbias, accR = f4{0.f, 0.f, 0.f, 0.f};      // one MFMA shape per accumulator
-                        accP = BM_MFMA_F16_K32(aP[0], w0.P[hf], accP);
-                        accR = BM_MFMA_F16_K16(aR[0], w0.R[hf], accR);
-                        accP = BM_MFMA_F16_K32(aP[1], w1.P[hf], accP);
-                        accR = BM_MFMA_F16_K16(aR[1], w1.R[hf], accR);
-                        accP = BM_MFMA_F16_K32(aP[2], w2.P[hf], accP);
-                        accR = BM_MFMA_F16_K16(aR[2], w2.R[hf], accR);
-                        cur[2 * r + hf][0] = relu_h4(to_h4(f4{accP[0] + accR[0], accP[1] + accR[1], accP[2] + accR[2], accP[3] + accR[3]}));
-                    }
-                    w0 = w1; w1 = w2;
-                    BM_SCHED_FENCE();
-                }
-                BM_PROF(4);
-                BM_PROF(5);
-                continue;
-            }
-            // 1x1 (linear): t = W_pw . cur  -> LDS image (fp16)
+            // 1x1 (linear): t = W_pw . cur  -> LDS image (fp16).  (Stage 0's 1x1 + depthwise composed into one dense 3x3 on the matrix
+            // pipe, without the image, measured 9 % slower: 16x the MACs at 16 channels, profiles/r2_osblock_dense_vs_base.txt.)
             if constexpr (KT == 1) {
                 const h4 a = *reinterpret_cast<const h4*>(lw + bp.light_pw + lane * 8);
 #pragma unroll
@@ -561,10 +422,12 @@ k_osblock(const _Float16* __restrict__ in, _Float16* __restrict__ out, const uns
     // share of the block time; LDS delivers 128 B/clk and leaves the L1 to the activations.
     //   [0, EPI_A)      this block's conv3 fragments, bias, downsample fragments (contiguous in the packed blob)
     //   [EPI_A, +EPI_T) fused transition: fragments + bias        [.., +EPI_P) RECON: previous block's conv3/bias/down
-    constexpr bool EPI = STAGE <= 1 || BM_STAGE2_EPI_LDS;
+    // Stage 2 reads them from L1: staging its conv3 (8 KiB) + bias + downsample 96 -> 128 (24 KiB), which outgrow its image,
+    // gained 1 % with the 4-workgroup build (docs/history/DESIGN_rounds_1-5.md, the round-2 variants) and was not kept.
+    constexpr bool EPI = STAGE <= 1;
     constexpr int KS3E = COUT / 32;
     constexpr int EPI_T = TRANS ? NCT * KS3E * 1024 + COUT * 4 : 0;
-    const int epi_a = (EPI && STAGE >= 1 && !RECON) ? (int)(bp.total - bp.conv3_a) : 0;     // (stage-1 RECON: no room left)
+    const int epi_a = (STAGE == 1 && !RECON) ? (int)(bp.total - bp.conv3_a) : 0;     // (stage-1 RECON: no room left)
     const unsigned char* ew = wts + bp.conv3_a;          // conv3_a-relative base of this block's epilogue operands
     const unsigned char* etr = wtr;
     const unsigned char* epv = RECON ? link.w + link.a0 : nullptr;      // a0-relative base of the previous block's operands
@@ -598,9 +461,11 @@ k_osblock(const _Float16* __restrict__ in, _Float16* __restrict__ out, const uns
             if constexpr (DOWN && CIN == 16) wdr[co] = *reinterpret_cast<const h4*>(ew + oda + (co * 64 + lane) * 8);
         }
     }
-    // Operands a tile's epilogue takes from memory: loaded one tile ahead of their use (BM_PREFETCH) -- with two workgroups
-    // per CU the round trip of these loads (L2 or further) was exposed once per tile.
-    constexpr bool EPI_PF = BM_PREFETCH_EPI == 1 || (BM_PREFETCH_EPI == 2 && STAGE == 1 && TRANS && !RECON);
+    // Operands a tile's epilogue takes from memory (block input for the shortcut / downsample, the hand-over tensors): loaded one
+    // tile ahead of their use in the stage-1 second block only.  Measured per kernel at 4096 crops (tools/osblock_prof.hip,
+    // profiles/r2_osblock_variants.txt): -6 % there, but +3 % / +7 % on the stage-0 RECON and stage-2 first blocks (they are at
+    // the 128-register budget: the second operand set spills).
+    constexpr bool EPI_PF = STAGE == 1 && TRANS && !RECON;
     struct TileIn {
         h8 bx[KIN];             // DOWN, wide input: the block input (downsample operand)
         h4 bx4;                 // DOWN, 16-channel input
@@ -686,7 +551,7 @@ k_osblock(const _Float16* __restrict__ in, _Float16* __restrict__ out, const uns
             y[co] = relu_h4(to_h4(acc));
         }
     };
-    // tile i's operands are in tin[i & 1]: loaded while tile i - 1 computes (BM_PREFETCH) or right before the use
+    // tile i's operands are in tin[i & 1]: loaded while tile i - 1 computes (EPI_PF) or right before the use
     TileIn tin[2];
     auto epi_begin = [&](int i_first) { if constexpr (EPI_PF) tile_loads(i_first, tin[i_first & 1]); };
     auto epi_tile = [&](int i, int i_next, h4 (&y)[NCT]) {          // i_next < 0: no further tile
@@ -784,6 +649,8 @@ k_osblock(const _Float16* __restrict__ in, _Float16* __restrict__ out, const uns
 // head: conv5 (1x1 C->C + ReLU) -> GAP -> FC(C->F) + BN1d + ReLU -> L2 norm
 // (osnet.py:310-315, 393-396; base_backend.py:206).  in [n][128 px][C]; one
 // workgroup (2 waves) per crop.  wts5: fragments [ct][ks] + bias; wfc: fp16 [F][C] (memory order) + fp32 bias.
+// The engine launches k_head_batched below; this kernel is kept as the reference the batched head is compared with
+// (emu_reid_head in tests/host_emu/emu_reid.cpp runs it), and no library build instantiates it.
 // ---------------------------------------------------------------------------
 template <int C, int F>
 __global__ void __launch_bounds__(128) k_head_fused(const _Float16* __restrict__ in, const unsigned char* __restrict__ wts5,
@@ -1090,30 +957,24 @@ __global__ void __launch_bounds__(512) k_stem_fused(const _Float16* __restrict__
 //      (crop pixels are read from HBM exactly once; boxes too large for the staging area take direct loads),
 //   2. cv2.resize's fixed-point bilinear + the normalisation table produce 32 new fp16 RGBX input rows
 //      into a 40-row LDS ring (rows are reused by the next band),
-//   3. wave w computes pooled row 8*band + w: three conv rows as MFMA k-steps over LDS B fragments
-//      (one ds_read_b128 per MFMA), vertical + horizontal max, store.
+//   3. conv rows as MFMA k-steps over LDS B fragments, vertical + horizontal max, store.
 // Same arithmetic (and bit-identical fp16 output) as k_crop_resize_rgbx + k_stem_fused.
 // ---------------------------------------------------------------------------
-// BM_STEM_STREAM = 1: in the conv phase a wave owns one 16-pixel column strip and FOUR pooled rows (nine conv rows) and
-// streams the 23 input rows of the strip once: one ds_read_b128 per input row feeds the 3-4 conv rows that row contributes to
-// (kernel rows ky of the same parity), each into its own accumulator in ascending ky -- the same sums in the same order as
-// BM_STEM_STREAM = 0 (a wave owns one pooled row across the width: 84 reads and 84 MFMAs per band against 23 and 63 here; the
-// phase was bound by the LDS read bandwidth, 1 KiB per MFMA).  The pooled pixel on a strip's first column needs the last conv
-// column of the strip to its left, which another wave computes: it crosses through a 4 KiB LDS edge buffer (double-buffered
-// by band parity) under the barrier that ends the band.
-#ifndef BM_STEM_STREAM
-#define BM_STEM_STREAM 1
-#endif
-// BM_STEM_ASYNC = 1: the source rows of band b + 1 are requested by asynchronous global -> LDS copies (global_load_lds_dword)
-// right after the barrier that ends band b's resampling -- the staging area is idle from there to band b + 1's resampling -- and
-// land under band b's convolution phase: no registers, no exposed load latency per band (a register prefetch had cost 1.5 %).
-#ifndef BM_STEM_ASYNC
-#define BM_STEM_ASYNC 1
-#endif
+// Conv phase: a wave owns one 16-pixel column strip and FOUR pooled rows (nine conv rows) and streams the 23 input rows of the
+// strip once: one ds_read_b128 per input row feeds the 3-4 conv rows that row contributes to (kernel rows ky of the same
+// parity), each into its own accumulator in ascending ky -- the same sums in the same order as a wave that owns one pooled row
+// across the width (84 reads and 84 MFMAs per band against 23 and 63 here; that phase was bound by the LDS read bandwidth,
+// 1 KiB per MFMA: profiles/r2_stem_stream_ab.txt).  The pooled pixel on a strip's first column needs the last conv column of
+// the strip to its left, which another wave computes: it crosses through a 4 KiB LDS edge buffer (double-buffered by band
+// parity) under the barrier that ends the band.
+// Staging: the source rows of band b + 1 are requested by asynchronous global -> LDS copies (global_load_lds_dword) right after
+// the barrier that ends band b's resampling -- the staging area is idle from there to band b + 1's resampling -- and land under
+// band b's convolution phase: no registers, no exposed load latency per band (a register prefetch had cost 1.5 %; against the
+// synchronous copy 0.769 -> 0.755 ms per 4096 crops, profiles/r3_stem_async_ab.txt).
 constexpr int RING_ROWS = 40;
 constexpr int RING_ROW_BYTES = STEM_COLS * 8;                    // 136 px * RGBX fp16
 constexpr int SRC_STAGE_BYTES = 20 * 1024;
-constexpr int STEM_EDGE_BYTES = BM_STEM_STREAM ? 2 * 2 * 4 * 4 * 16 * 4 : 0;   // [band parity][half][strip][pooled row][channel] fp32
+constexpr int STEM_EDGE_BYTES = 2 * 2 * 4 * 4 * 16 * 4;          // [band parity][half][strip][pooled row][channel] fp32
 constexpr int STEM_LUT_BYTES = 768 * 4;                          // normalisation table, 4-byte entries (fp16 in the low half)
 constexpr int STEM2_LDS = RING_ROWS * RING_ROW_BYTES + SRC_STAGE_BYTES + STEM_LUT_BYTES + 256 * 8 + STEM_EDGE_BYTES;   // ring, staging, LUT, y table, edges
 // the fp32-grade stem keeps its seven lo fragments in LDS (one ds_read_b128 per lo MFMA) instead of 28 registers: at <= 128
@@ -1200,10 +1061,8 @@ __device__ __forceinline__ void stem_resize_fused_body(const uint8_t* const* fra
             unsigned char* dst0 = stage + rr * b.pitch;
             for (int cw = lane; cw < ndw; cw += 64) {
                 const uint8_t* src = src0 + 4 * cw;
-                if (src + 4 <= frame_end) {
-                    if constexpr (BM_STEM_ASYNC) BM_GLDS4(src, dst0 + 4 * (cw - lane), lane);
-                    else *reinterpret_cast<unsigned*>(dst0 + 4 * cw) = *reinterpret_cast<const unsigned*>(src);
-                } else {                                  // tail of the frame: stay inside the allocation
+                if (src + 4 <= frame_end) BM_GLDS4(src, dst0 + 4 * (cw - lane), lane);
+                else {                                // tail of the frame: stay inside the allocation
                     unsigned v = 0;
                     for (int q = 0; q < 4 && src + q < frame_end; ++q) v |= (unsigned)src[q] << (8 * q);
                     *reinterpret_cast<unsigned*>(dst0 + 4 * cw) = v;
@@ -1211,14 +1070,13 @@ __device__ __forceinline__ void stem_resize_fused_body(const uint8_t* const* fra
             }
         }
     };
-    if constexpr (BM_STEM_ASYNC) stage_rows(band_geom(0));
+    stage_rows(band_geom(0));
 #pragma unroll 1
     for (int band = 0; band < 8; ++band) {
         const BandGeom bg = band_geom(band);
         const int pr0 = bg.pr0, pr1 = bg.pr1, sy_lo = bg.sy_lo, pitch = bg.pitch;
         const bool staged = bg.staged;
-        if constexpr (BM_STEM_ASYNC) BM_WAIT_VM0();         // this wave's copies of the band's rows have landed
-        else stage_rows(bg);
+        BM_WAIT_VM0();         // this wave's copies of the band's rows have landed
         BM_PROF(1);
         __syncthreads();
         BM_PROF(2);
@@ -1326,8 +1184,7 @@ __device__ __forceinline__ void stem_resize_fused_body(const uint8_t* const* fra
         BM_PROF(3);
         __syncthreads();
         BM_PROF(4);
-        if constexpr (BM_STEM_ASYNC) { if (band + 1 < 8) stage_rows(band_geom(band + 1)); }     // the staging area is idle until then
-#if BM_STEM_STREAM
+        if (band + 1 < 8) stage_rows(band_geom(band + 1));     // the staging area is idle until then
         // ---- 3. conv rows + pooling: strip t (16 conv pixels), pooled rows oy0 .. oy0 + 3 ----
         {
             const int t = wave & 3, half = wave >> 2;
@@ -1388,46 +1245,6 @@ __device__ __forceinline__ void stem_resize_fused_body(const uint8_t* const* fra
                 }
             }
         }
-#else
-        static_assert(!HP, "the fp32-grade stem exists for the strip-wise conv phase (BM_STEM_STREAM)");
-        // ---- 3. conv rows + pooling for pooled row oy ----
-        const int oy = 8 * band + wave;
-        f4 vprev = f4{0.f, 0.f, 0.f, 0.f};       // vertical max of the previous tile (for the left neighbour of lane 0)
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            f4 vm = f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int dc = -1; dc <= 1; ++dc) {
-                const int cy = 2 * oy + dc;
-                if (cy < 0 || cy > 127) continue;          // wave-uniform
-                f4 acc = bias;
-                const int cx = t * 16 + l16;
-#pragma unroll
-                for (int ky = 0; ky < 7; ++ky) {
-                    const int slot = (2 * cy + ky) % RING_ROWS;
-                    const h8 b = *reinterpret_cast<const h8*>(ring + slot * RING_ROW_BYTES + (2 * cx + 2 * g) * 8);
-                    acc = BM_MFMA_F16_K32(a[ky], b, acc);
-                }
-                vm = max4(vm, relu4(acc));
-            }
-            f4 m = vm;
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) {   // all values are >= 0 (post-ReLU), so a missing neighbour reads as 0
-                const float right = BM_ROW_SHL1_F32(vm[rr]);
-                float left = BM_ROW_SHR1_F32(vm[rr]);
-                const float left_prev = BM_ROW_ROR1_F32(vprev[rr]);
-                if (l16 == 0) left = t > 0 ? left_prev : 0.f;
-                const float mm = m[rr] > right ? m[rr] : right;
-                m[rr] = mm > left ? mm : left;
-            }
-            if ((l16 & 1) == 0) {
-                const int p = oy * 32 + t * 8 + (l16 >> 1);
-                *reinterpret_cast<h4*>(yout + (long)p * 16 + g * 4) = to_h4(m);
-            }
-            vprev = vm;
-        }
-        __syncthreads();
-#endif
         BM_PROF(7);
     }
     BM_PROF_FLUSH();

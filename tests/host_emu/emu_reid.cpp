@@ -18,7 +18,6 @@ EmuDim3 gridDim;
 EmuBlock* g_emu_block = nullptr;
 unsigned char* g_emu_dynamic_lds = nullptr;
 static int g_stage1_handover = 0;
-static int g_head_per_crop = 0;
 EmuMfmaBuf* g_emu_mfma = nullptr;
 
 namespace {
@@ -67,7 +66,6 @@ void unpack_act(const _Float16* src, float* dst, long n_pix, int C) {
 extern "C" {
 
 void emu_reid_set_stage1_handover(int on) { g_stage1_handover = on; }
-void emu_reid_set_head_per_crop(int on) { g_head_per_crop = on; }
 
 // crops: normalised fp32 NHWC (n, 256, 128, 3).  stage_out[k] (may be null) receives the fp32 NHWC
 // activation after: 0 stem+maxpool, 1..2 stage-1 blocks, 3 transition, 4..5 blocks, 6 transition,
@@ -255,8 +253,7 @@ int emu_reid_forward(const float* blob, long n_floats, const float* crops, int n
     pack_fc(w + L.fc_w, w + L.fc_b, 512, 128, wfc);
     {
         const _Float16* in = cur; const unsigned char* p5 = w5.data(); const unsigned char* pf = wfc.data();
-        if (g_head_per_crop) launch(n, 1, 128, [=]() { k_head_fused<128, 512>(in, p5, pf, feats, nullptr, nullptr); });
-        else launch((n + HEAD_NB - 1) / HEAD_NB, 1, 256, [=]() { k_head_batched<128, 512>(in, p5, pf, feats, nullptr, nullptr, n); });
+        launch((n + HEAD_NB - 1) / HEAD_NB, 1, 256, [=]() { k_head_batched<128, 512>(in, p5, pf, feats, nullptr, nullptr, n); });
     }
     return 0;
 }

@@ -30,8 +30,8 @@ def _build(no_vm_wait=False, immediate=False):
 @pytest.mark.parametrize("stage1_handover", [0, 1])
 @pytest.mark.skipif(CLANG is None, reason="needs a host clang with _Float16")
 def test_fused_reid_kernels_emulated_vs_oracle(stage1_handover):
-    """stage1_handover = 1: stage 1 also runs as an EMIT / RECON pair (engine build flag BM_STAGE1_HANDOVER, off by default
-    until it has been measured on the device)."""
+    """stage1_handover = 1: stage 1 also runs as an EMIT / RECON pair (engine build flag BM_STAGE1_HANDOVER, off by default:
+    measured on the device as a 0.2 % gain, docs/history/DESIGN_rounds_1-5.md, the round-2 variants)."""
     import torch
 
     from boxmot_amd.reid_weights import pack_osnet, reference_init_state_dict

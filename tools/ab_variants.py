@@ -2,10 +2,12 @@
 
 Builds `libboxmot_hip` once per variant into tools/_build/ (run this part in the build container -- hipcc cross-compiles),
 then, on the GPU box, runs the ReID parity tests and `bench.py --no-cpu-baseline` against each and prints one line per
-variant.  The variants are the off-by-default flags of reid_engine.hpp / reid_fused.hpp:
+variant.  What remains selectable in the fp16 OSNet-x0.25 family is the shipped build (`base`) and the stage-1 EMIT / RECON
+hand-over (`s1_handover`, BM_STAGE1_HANDOVER in reid_fused.hpp); the other round-2 / round-3 variants were measured, left at
+their shipped values and removed from the source (profiles/README.md, profiles/fp16_switch_prune_isa.txt):
 
-    python tools/ab_variants.py build                      # here
-    gpurun -- 'python tools/ab_variants.py run'            # there
+    python tools/ab_variants.py build                      # in the build container
+    python tools/ab_variants.py run                        # on the GPU box
 """
 import json
 import os
@@ -17,15 +19,7 @@ ROOT = Path(__file__).resolve().parents[1]
 OUT = ROOT / "tools" / "_build"
 VARIANTS = {
     "base": [],
-    "dense": ["-DBM_DENSE_LIGHT=1"],                  # stage-0 LightConv as a dense 3x3 on the matrix pipe
-    "head_per_crop": ["-DBM_HEAD_PER_CROP=1"],        # the round-1 head instead of k_head_batched
-    "no_prefetch": ["-DBM_PREFETCH_CONV1=0", "-DBM_PREFETCH_EPI=0"],     # round-1 load order in conv1 / epilogue
-    "pf_epi_all": ["-DBM_PREFETCH_EPI=1"],
-    "s1_handover": ["-DBM_STAGE1_HANDOVER=1"],
-    "s2_epi_lds": ["-DBM_STAGE2_EPI_LDS=1"],
-    "s2_occ4": ["-DBM_STAGE2_OCC4=1"],
-    "s2_both": ["-DBM_STAGE2_EPI_LDS=1", "-DBM_STAGE2_OCC4=1"],
-    "all": ["-DBM_STAGE1_HANDOVER=1", "-DBM_STAGE2_EPI_LDS=1", "-DBM_STAGE2_OCC4=1"],
+    "s1_handover": ["-DBM_STAGE1_HANDOVER=1"],        # stage 1 as an EMIT / RECON block pair, like stage 0
 }
 
 
