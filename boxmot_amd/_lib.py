@@ -129,6 +129,12 @@ class DetPostTiledConfig(ctypes.Structure):
     _fields_ = [("base", DetPostConfig), ("n_tiles", ctypes.c_int), ("merge", ctypes.c_int)]
 
 
+class DetPostExtraConfig(ctypes.Structure):
+    """``BoxMOTHipDetPostExtraConfig`` (include/boxmot_hip.h)."""
+
+    _fields_ = [("base", DetPostConfig), ("n_tiles", ctypes.c_int), ("merge", ctypes.c_int), ("n_extra", ctypes.c_int), ("extra_kind", ctypes.c_int)]
+
+
 class Letterbox(ctypes.Structure):
     """``BoxMOTHipLetterbox`` (include/boxmot_hip.h)."""
 
@@ -263,6 +269,8 @@ SIGNATURES = {
     "boxmot_hip_ingest_letterbox_tiles": (_I, [_VP, _I, _I, _I, _VP, ctypes.POINTER(Letterbox), _VP, _VP]),
     "boxmot_hip_detpost_create_tiled": (_VP, [ctypes.POINTER(DetPostTiledConfig)]),
     "boxmot_hip_detpost_run_tiled": (_I, [_VP, _I, _VP, _I, c_double_p, _VP, _I, _VP, _VP]),
+    "boxmot_hip_detpost_create_extra": (_VP, [ctypes.POINTER(DetPostExtraConfig)]),
+    "boxmot_hip_detpost_run_extra": (_I, [_VP, _I, _VP, _I, c_double_p, _VP, _I, _VP, _VP, _VP, _VP]),
     "boxmot_hip_last_error": (ctypes.c_char_p, []),
     "boxmot_hip_device_count": (_I, []),
     "boxmot_hip_botsort_device": (_I, [_VP]),

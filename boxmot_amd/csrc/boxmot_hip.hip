@@ -396,8 +396,12 @@ struct BoxMOTHipDetPost : DeviceBound {
     int n_tiles = 0, merge = 0;
     DetPostGeomTable<bm::DetPostGeom> geom;         // [n_streams]
     DetPostGeomTable<bm::DetPostTileGeom> tgeom;    // [n_streams][n_tiles]
+    // a handle with per-anchor extras (boxmot_hip_detpost_create_extra, csrc/det_post_extra.hpp), tiled or not
+    int n_extra = 0, extra_kind = 0;
+    int* d_src = nullptr;                           // [n_streams][max_det]: where the source anchors go when the caller gives no d_src
     ~BoxMOTHipDetPost() {
         if (done) { if (ran) (void)hipEventSynchronize(done); (void)hipEventDestroy(done); }
+        if (d_src) (void)hipFree(d_src);
         if (d_keys) (void)hipFree(d_keys);
         if (d_cls) (void)hipFree(d_cls);
         if (d_counters) (void)hipFree(d_counters);
@@ -421,11 +425,13 @@ void detpost_allow_lds(K select_f32, K select_f16, size_t lds) {
     BM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(select_f16), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
 }
 
-// what both run entry points check before they read their geometry rows; tiled: which of the two was called
+// what the run entry points check before they read their geometry rows; tiled, extra: which of them was called
 void detpost_check_run(const BoxMOTHipDetPost* handle, bool tiled, int n_streams, const void* d_pred, int dtype, const double* geom, const float* d_dets,
-                       int out_stride_rows, const int* d_det_rows) {
+                       int out_stride_rows, const int* d_det_rows, bool extra = false) {
     if (!handle) throw std::runtime_error("boxmot_hip: null detpost handle");
     const BoxMOTHipDetPostConfig& c = handle->cfg;
+    if (!extra && handle->n_extra) throw std::runtime_error("boxmot_hip: a detpost handle with extras is run with boxmot_hip_detpost_run_extra");
+    if (extra && !handle->n_extra) throw std::runtime_error("boxmot_hip: boxmot_hip_detpost_run_extra needs a handle of boxmot_hip_detpost_create_extra");
     if (!tiled && handle->n_tiles) throw std::runtime_error("boxmot_hip: a tiled detpost handle is run with boxmot_hip_detpost_run_tiled");
     if (tiled && !handle->n_tiles) throw std::runtime_error("boxmot_hip: boxmot_hip_detpost_run_tiled needs a handle of boxmot_hip_detpost_create_tiled");
     if (n_streams < 1 || n_streams > c.n_streams)
@@ -3184,11 +3190,20 @@ int boxmot_hip_ingest_letterbox_tiles(BoxMOTHipIngest* handle, int slot, int n_s
 
 // ---- detection post-processing (csrc/det_post.hpp has the definition) ----
 namespace {
-// the create entry points; oc: the oriented options, or null for an axis-aligned handle; tc: the tiled options, or null
-BoxMOTHipDetPost* detpost_create(const BoxMOTHipDetPostConfig* c, const BoxMOTHipDetPostObbConfig* oc, const BoxMOTHipDetPostTiledConfig* tc = nullptr) {
+// the create entry points; oc: the oriented options, or null for an axis-aligned handle; tc: the tiled options, or null; ec: the
+// per-anchor extras (with tc made of its n_tiles and merge when tiled), or null
+BoxMOTHipDetPost* detpost_create(const BoxMOTHipDetPostConfig* c, const BoxMOTHipDetPostObbConfig* oc, const BoxMOTHipDetPostTiledConfig* tc = nullptr,
+                                 const BoxMOTHipDetPostExtraConfig* ec = nullptr) {
     BoxMOTHipDetPost* h = nullptr;
     const int ok = guard([&]() {
         if (!c) throw std::runtime_error("boxmot_hip: null detpost config");
+        if (ec && (ec->n_extra < 1 || ec->n_extra > bm::DP_EXTRA_MAX))
+            throw std::runtime_error("boxmot_hip: detpost n_extra must be within 1.." + std::to_string(bm::DP_EXTRA_MAX) + ", got " + std::to_string(ec->n_extra));
+        if (ec && (ec->extra_kind < 0 || ec->extra_kind >= bm::DP_EXTRA_KINDS))
+            throw std::runtime_error("boxmot_hip: unknown detpost extra_kind " + std::to_string(ec->extra_kind) + " (0 raw, 1 kpt2, 2 kpt3)");
+        if (ec && ec->n_extra % bm::detpost_extra_group(ec->extra_kind))
+            throw std::runtime_error("boxmot_hip: detpost n_extra " + std::to_string(ec->n_extra) + " is no multiple of the " +
+                                     std::to_string(bm::detpost_extra_group(ec->extra_kind)) + " values per keypoint of extra_kind " + std::to_string(ec->extra_kind));
         if (oc && c->layout != 0)
             throw std::runtime_error("boxmot_hip: an oriented detpost handle needs base.layout 0 (cn), got " + std::to_string(c->layout));
         if (oc && oc->nms_mode != 0 && oc->nms_mode != 1)
@@ -3201,6 +3216,7 @@ BoxMOTHipDetPost* detpost_create(const BoxMOTHipDetPostConfig* c, const BoxMOTHi
         if (c->max_candidates < bm::DP_K_MIN || c->max_candidates > bm::DP_K_MAX)
             throw std::runtime_error("boxmot_hip: detpost max_candidates must be within 64..4096, got " + std::to_string(c->max_candidates));
         if (c->max_det < 1) throw std::runtime_error("boxmot_hip: detpost max_det must be >= 1");
+        if (ec && (long)c->max_det * ec->n_extra > (1L << 30)) throw std::runtime_error("boxmot_hip: detpost max_det * n_extra is too large");
         if ((long)c->n_streams * c->n_anchors > (1L << 30)) throw std::runtime_error("boxmot_hip: detpost n_streams * n_anchors is too large");
         if (tc && (tc->n_tiles < 1 || tc->n_tiles > bm::DP_TILES_MAX))
             throw std::runtime_error("boxmot_hip: detpost n_tiles must be within 1.." + std::to_string(bm::DP_TILES_MAX) + ", got " + std::to_string(tc->n_tiles));
@@ -3215,6 +3231,7 @@ BoxMOTHipDetPost* detpost_create(const BoxMOTHipDetPostConfig* c, const BoxMOTHi
         h->cfg.class_allow = nullptr;
         if (oc) { h->obb = 1; h->nms_mode = oc->nms_mode; h->regularize = oc->regularize ? 1 : 0; }
         if (tc) { h->n_tiles = tc->n_tiles; h->merge = tc->merge; }
+        if (ec) { h->n_extra = ec->n_extra; h->extra_kind = ec->extra_kind; }
         const size_t SA = (size_t)c->n_streams * n_tensors * c->n_anchors;
         void* p = nullptr;
         BM_HIP(hipMalloc(&p, SA * sizeof(uint32_t))); h->d_keys = static_cast<uint32_t*>(p);
@@ -3228,17 +3245,72 @@ BoxMOTHipDetPost* detpost_create(const BoxMOTHipDetPostConfig* c, const BoxMOTHi
             BM_HIP(hipMemcpy(h->d_allow, allow.data(), allow.size(), hipMemcpyHostToDevice));
         }
         BM_HIP(hipEventCreateWithFlags(&h->done, hipEventDisableTiming));
+        if (ec) { BM_HIP(hipMalloc(&p, (size_t)c->n_streams * c->max_det * sizeof(int))); h->d_src = static_cast<int*>(p); }
         if (tc) {
             h->tgeom.create((size_t)c->n_streams * tc->n_tiles);
-            detpost_allow_lds(bm::k_detpost_select_tiled<float>, bm::k_detpost_select_tiled<_Float16>, bm::detpost_lds_bytes(c->max_candidates));
+            if (ec) detpost_allow_lds(bm::k_detpost_select_tiled_src<float>, bm::k_detpost_select_tiled_src<_Float16>, bm::detpost_lds_bytes(c->max_candidates));
+            else detpost_allow_lds(bm::k_detpost_select_tiled<float>, bm::k_detpost_select_tiled<_Float16>, bm::detpost_lds_bytes(c->max_candidates));
         } else {
             h->geom.create((size_t)c->n_streams);
             if (oc) detpost_allow_lds(bm::k_detpost_select_obb<float>, bm::k_detpost_select_obb<_Float16>, bm::detpost_obb_lds_bytes(c->max_candidates));
+            else if (ec) detpost_allow_lds(bm::k_detpost_select_src<float>, bm::k_detpost_select_src<_Float16>, bm::detpost_lds_bytes(c->max_candidates));
             else detpost_allow_lds(bm::k_detpost_select<float>, bm::k_detpost_select<_Float16>, bm::detpost_lds_bytes(c->max_candidates));
         }
     });
     if (!ok) { const std::string e = g_last_error; destroy_on(h); g_last_error = e; return nullptr; }
     return h;
+}
+
+// the checked geometry rows of an untiled / a tiled call, and the kernels' arguments (d_extra / d_src: a handle with extras)
+void detpost_geom_rows(const double* geom, int n_streams, std::vector<bm::DetPostGeom>& g) {
+    g.resize(n_streams);
+    for (int s = 0; s < n_streams; ++s) {
+        const double* v = geom + 5 * s;
+        if (!(v[0] > 0.0) || !std::isfinite(v[0]) || !(v[3] >= 1.0) || !(v[4] >= 1.0) || !std::isfinite(v[1]) || !std::isfinite(v[2]) ||
+            !std::isfinite(v[3]) || !std::isfinite(v[4]))
+            throw std::runtime_error("boxmot_hip: detpost stream " + std::to_string(s) + ": geometry needs gain > 0 and a frame of >= 1 x 1 (gain " +
+                                     std::to_string(v[0]) + ", rows " + std::to_string(v[3]) + ", cols " + std::to_string(v[4]) + ")");
+        g[s] = bm::DetPostGeom{(float)v[0], (float)v[1], (float)v[2], (float)v[3], (float)v[4]};
+    }
+}
+void detpost_tile_geom_rows(const double* geom, int n_streams, int T, std::vector<bm::DetPostTileGeom>& g) {
+    g.resize((size_t)n_streams * T);
+    for (size_t k = 0; k < g.size(); ++k) {
+        const double* v = geom + 7 * k;
+        bool finite = true;
+        for (int q = 0; q < 7; ++q) finite = finite && std::isfinite(v[q]);
+        if (!finite || !(v[0] > 0.0) || !(v[5] >= 1.0) || !(v[6] >= 1.0))
+            throw std::runtime_error("boxmot_hip: detpost stream " + std::to_string(k / T) + " tile " + std::to_string(k % T) +
+                                     ": geometry needs finite values, gain > 0 and a tile of >= 1 x 1 (gain " + std::to_string(v[0]) + ", w " +
+                                     std::to_string(v[5]) + ", h " + std::to_string(v[6]) + ")");
+        g[k] = bm::DetPostTileGeom{(float)v[0], (float)v[1], (float)v[2], (float)v[3], (float)v[4], (float)v[5], (float)v[6]};
+    }
+}
+bm::DetPostArgs detpost_args(const BoxMOTHipDetPost* handle, const void* d_pred, float* d_dets, int out_stride_rows, int* d_det_rows,
+                             float* d_extra = nullptr, int* d_src = nullptr) {
+    const BoxMOTHipDetPostConfig& c = handle->cfg;
+    bm::DetPostArgs a{d_pred, handle->n_tiles ? nullptr : handle->geom.d, handle->d_allow, handle->d_keys, handle->d_cls, d_dets, d_det_rows, handle->d_counters,
+                      c.n_anchors, c.n_classes, c.layout, c.max_candidates, c.max_det, c.agnostic ? 1 : 0, out_stride_rows, c.conf_thres,
+                      c.iou_thres, handle->obb, handle->nms_mode, handle->regularize};
+    if (handle->n_extra) {
+        a.src = d_src ? d_src : handle->d_src;
+        a.src_stride = d_src ? out_stride_rows : c.max_det;
+        a.extra = d_extra; a.n_extra = handle->n_extra; a.extra_kind = handle->extra_kind;
+    }
+    return a;
+}
+// an untiled or a tiled run, by the handle's kind
+void detpost_run_checked(BoxMOTHipDetPost* handle, int n_streams, int dtype, const double* geom, const bm::DetPostArgs& a, void* hip_stream) {
+    if (handle->n_tiles) {
+        const bm::DetPostTiledArgs ta{a, handle->tgeom.d, handle->n_tiles, handle->merge};
+        std::vector<bm::DetPostTileGeom> g;
+        detpost_tile_geom_rows(geom, n_streams, handle->n_tiles, g);
+        detpost_run(handle, handle->tgeom, g, n_streams, hip_stream, [&](DetPostLaunch& on) { bm::detpost_launch_tiled(on, ta, n_streams, dtype); });
+    } else {
+        std::vector<bm::DetPostGeom> g;
+        detpost_geom_rows(geom, n_streams, g);
+        detpost_run(handle, handle->geom, g, n_streams, hip_stream, [&](DetPostLaunch& on) { bm::detpost_launch(on, a, n_streams, dtype); });
+    }
 }
 }  // namespace
 
@@ -3255,20 +3327,7 @@ int boxmot_hip_detpost_run(BoxMOTHipDetPost* handle, int n_streams, const void* 
                            int out_stride_rows, int* d_det_rows, void* hip_stream) {
     return guard_on(handle, [&]() {
         detpost_check_run(handle, false, n_streams, d_pred, dtype, geom, d_dets, out_stride_rows, d_det_rows);
-        const BoxMOTHipDetPostConfig& c = handle->cfg;
-        std::vector<bm::DetPostGeom> g(n_streams);
-        for (int s = 0; s < n_streams; ++s) {
-            const double* v = geom + 5 * s;
-            if (!(v[0] > 0.0) || !std::isfinite(v[0]) || !(v[3] >= 1.0) || !(v[4] >= 1.0) || !std::isfinite(v[1]) || !std::isfinite(v[2]) ||
-                !std::isfinite(v[3]) || !std::isfinite(v[4]))
-                throw std::runtime_error("boxmot_hip: detpost stream " + std::to_string(s) + ": geometry needs gain > 0 and a frame of >= 1 x 1 (gain " +
-                                         std::to_string(v[0]) + ", rows " + std::to_string(v[3]) + ", cols " + std::to_string(v[4]) + ")");
-            g[s] = bm::DetPostGeom{(float)v[0], (float)v[1], (float)v[2], (float)v[3], (float)v[4]};
-        }
-        const bm::DetPostArgs a{d_pred, handle->geom.d, handle->d_allow, handle->d_keys, handle->d_cls, d_dets, d_det_rows, handle->d_counters,
-                                c.n_anchors, c.n_classes, c.layout, c.max_candidates, c.max_det, c.agnostic ? 1 : 0, out_stride_rows, c.conf_thres,
-                                c.iou_thres, handle->obb, handle->nms_mode, handle->regularize};
-        detpost_run(handle, handle->geom, g, n_streams, hip_stream, [&](DetPostLaunch& on) { bm::detpost_launch(on, a, n_streams, dtype); });
+        detpost_run_checked(handle, n_streams, dtype, geom, detpost_args(handle, d_pred, d_dets, out_stride_rows, d_det_rows), hip_stream);
     });
 }
 
@@ -3281,24 +3340,23 @@ int boxmot_hip_detpost_run_tiled(BoxMOTHipDetPost* handle, int n_streams, const 
                                  int out_stride_rows, int* d_det_rows, void* hip_stream) {
     return guard_on(handle, [&]() {
         detpost_check_run(handle, true, n_streams, d_pred, dtype, geom, d_dets, out_stride_rows, d_det_rows);
-        const BoxMOTHipDetPostConfig& c = handle->cfg;
-        const int T = handle->n_tiles;
-        std::vector<bm::DetPostTileGeom> g((size_t)n_streams * T);
-        for (size_t k = 0; k < g.size(); ++k) {
-            const double* v = geom + 7 * k;
-            bool finite = true;
-            for (int q = 0; q < 7; ++q) finite = finite && std::isfinite(v[q]);
-            if (!finite || !(v[0] > 0.0) || !(v[5] >= 1.0) || !(v[6] >= 1.0))
-                throw std::runtime_error("boxmot_hip: detpost stream " + std::to_string(k / T) + " tile " + std::to_string(k % T) +
-                                         ": geometry needs finite values, gain > 0 and a tile of >= 1 x 1 (gain " + std::to_string(v[0]) + ", w " +
-                                         std::to_string(v[5]) + ", h " + std::to_string(v[6]) + ")");
-            g[k] = bm::DetPostTileGeom{(float)v[0], (float)v[1], (float)v[2], (float)v[3], (float)v[4], (float)v[5], (float)v[6]};
-        }
-        const bm::DetPostTiledArgs a{bm::DetPostArgs{d_pred, nullptr, handle->d_allow, handle->d_keys, handle->d_cls, d_dets, d_det_rows, handle->d_counters,
-                                                     c.n_anchors, c.n_classes, c.layout, c.max_candidates, c.max_det, c.agnostic ? 1 : 0, out_stride_rows,
-                                                     c.conf_thres, c.iou_thres, 0, 0, 0},
-                                     handle->tgeom.d, T, handle->merge};
-        detpost_run(handle, handle->tgeom, g, n_streams, hip_stream, [&](DetPostLaunch& on) { bm::detpost_launch_tiled(on, a, n_streams, dtype); });
+        detpost_run_checked(handle, n_streams, dtype, geom, detpost_args(handle, d_pred, d_dets, out_stride_rows, d_det_rows), hip_stream);
+    });
+}
+
+BoxMOTHipDetPost* boxmot_hip_detpost_create_extra(const BoxMOTHipDetPostExtraConfig* c) {
+    if (!c) { g_last_error = "boxmot_hip: null detpost config"; return nullptr; }
+    const BoxMOTHipDetPostTiledConfig tc{c->base, c->n_tiles, c->merge};
+    return detpost_create(&c->base, nullptr, c->n_tiles ? &tc : nullptr, c);        // n_tiles 0: untiled
+}
+
+int boxmot_hip_detpost_run_extra(BoxMOTHipDetPost* handle, int n_streams, const void* d_pred, int dtype, const double* geom, float* d_dets,
+                                 int out_stride_rows, int* d_det_rows, float* d_extra, int* d_src, void* hip_stream) {
+    return guard_on(handle, [&]() {
+        detpost_check_run(handle, handle && handle->n_tiles, n_streams, d_pred, dtype, geom, d_dets, out_stride_rows, d_det_rows, true);
+        if (!d_extra) throw std::runtime_error("boxmot_hip: null detpost d_extra");
+        if ((uintptr_t)d_extra % 4 || (uintptr_t)d_src % 4) throw std::runtime_error("boxmot_hip: detpost d_extra and d_src must be aligned to their element size");
+        detpost_run_checked(handle, n_streams, dtype, geom, detpost_args(handle, d_pred, d_dets, out_stride_rows, d_det_rows, d_extra, d_src), hip_stream);
     });
 }
 

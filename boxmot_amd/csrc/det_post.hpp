@@ -34,6 +34,8 @@
 // 6. Counters.  counters[s] = {anchors that passed step 1, candidates after step 2, candidates kept by NMS before the max_det cut}.
 // The oriented layout "cn_obb" (layout 0 with obb = 1: one more channel row, the angle, after the classes; 7-column rows; rotated NMS)
 // is defined at the top of det_post_obb.hpp; it shares the score kernels, stages a-c and the kernel sequence below.
+// Heads with E more values per anchor after the class scores (pose keypoints, mask coefficients) are defined at the top of
+// det_post_extra.hpp: steps 1-6 read none of them, steps 7-8 write the source anchor and the extras of every emitted row.
 // (Parity with torchvision / Ultralytics on real detector output is not pinned by any test: tests/detpost_ref.py restates this
 // definition in NumPy, and the kernels are compared with that, bit for bit.)
 //
@@ -60,6 +62,7 @@
 //          the carry-over to the later chunks.  The stage is explained once, above dp_finish; the oriented kernel and the tiled
 //          one of det_post_tiled.hpp have the same stage written out with their record, their "j suppresses i" and their row.
 //          dp_finish then writes d_det_rows and the counters (all three kernels).
+//   k_detpost_extra<T>   only on a head with extras (det_post_extra.hpp): third on the same stream, the extras of the emitted rows.
 //   No floating-point atomic anywhere.  LDS: 8 + 16 + 4 + 1 bytes per candidate slot (K rounded up to a power of two) + 1.6 KB:
 //   31 KB at the default K = 1024, 118 KB at K = 4096, of the 160 KB of a CU.
 #pragma once
@@ -78,6 +81,7 @@ constexpr int DP_SCORE_THREADS = 256, DP_SCORE_VEC_THREADS = 64, DP_THREADS = 51
 constexpr int DP_LDS_FIXED = (256 + 16 + 8) * 4 + (DP_CHUNK + 1) * 8 + 8;      // histogram, wave sums, scalars, matrix rows + live mask (bytes)
 
 struct DetPostGeom { float gain, top, left, rows, cols; };         // per stream: LetterboxGeometry as to_frame uses it
+struct DetPostTileGeom { float gain, top, left, x0, y0, w, h; };   // per (stream, tile) of a tiled call (det_post_tiled.hpp)
 
 struct DetPostArgs {
     const void* pred;               // (S, 4 + nc, A) or (S, A, 5 + nc)
@@ -91,6 +95,10 @@ struct DetPostArgs {
     int A, nc, layout, K, max_det, agnostic, out_stride;
     float conf_thres, iou_thres;
     int obb, nms_mode, regularize;  // the oriented layout "cn_obb" (det_post_obb.hpp): one angle row after the classes; 0 greedy / 1 fast
+    // per-anchor extras (det_post_extra.hpp); all zero / null: a head without them, every address what it is without these fields
+    int* src;                       // [S][src_stride] the anchor of every emitted row; set whenever n_extra > 0 (the caller's block or a scratch)
+    float* extra;                   // [S][out_stride][n_extra]
+    int src_stride, n_extra, extra_kind;                        // n_extra: values per anchor after the class scores; 0 raw / 1 kpt2 / 2 kpt3
 };
 
 __host__ __device__ inline int detpost_slots(int K) { int p = DP_CHUNK; while (p < K) p <<= 1; return p; }
@@ -102,9 +110,14 @@ __device__ inline float dp_load(const float* p, long i) { return p[i]; }
 __device__ inline float dp_load(const _Float16* p, long i) { return (float)p[i]; }
 
 // element index of channel c (0..3 box, then the layout's own columns) of anchor a of stream s; the channel-major layout has
-// 4 + nc channels, and one more, the angle, when oriented
+// 4 + nc channels, and one more, the angle, when oriented.  EXTRA: n_extra more per anchor in both layouts (det_post_extra.hpp) --
+// a compile-time switch, so that the select kernels of a head without extras keep, instruction for instruction, the code they had
+// before there were any (measured: with the sum read at run time, two more scalar instructions, k_detpost_select ran 2.6 - 3.2 %
+// longer, far outside its run-to-run spread: profiles/detpost_extra_timing.txt)
+template <bool EXTRA = false>
 __device__ inline long dp_at(const DetPostArgs& g, int s, int a, int c) {
-    return g.layout == 0 ? ((long)s * (4 + g.nc + g.obb) + c) * g.A + a : ((long)s * g.A + a) * (5 + g.nc) + c;
+    const int x = EXTRA ? g.n_extra : 0;
+    return g.layout == 0 ? ((long)s * (4 + g.nc + g.obb + x) + c) * g.A + a : ((long)s * g.A + a) * (5 + g.nc + x) + c;
 }
 __device__ inline bool dp_finite(float v) { return fabsf(v) < INFINITY; }       // false for a NaN and for +-inf
 
@@ -114,7 +127,7 @@ __global__ void __launch_bounds__(DP_SCORE_THREADS) k_detpost_score(DetPostArgs 
     if (a >= g.A) return;
     const T* pred = static_cast<const T*>(g.pred);
     const int first = g.layout == 0 ? 4 : 5;
-    const long base = dp_at(g, s, a, first), step = g.layout == 0 ? (long)g.A : 1L;
+    const long base = dp_at<true>(g, s, a, first), step = g.layout == 0 ? (long)g.A : 1L;
     float best = -INFINITY;
     int cls = 0;
     for (int c = 0; c < g.nc; ++c) {
@@ -143,7 +156,7 @@ __global__ void __launch_bounds__(DP_SCORE_VEC_THREADS) k_detpost_score_cn_vec(D
     typedef typename DpVec<T>::type V;
     const int s = (int)blockIdx.y, a0 = ((int)blockIdx.x * DP_SCORE_VEC_THREADS + (int)threadIdx.x) * N;
     if (a0 >= g.A) return;
-    const T* row = static_cast<const T*>(g.pred) + ((long)s * (4 + g.nc + g.obb) + 4) * g.A + a0;
+    const T* row = static_cast<const T*>(g.pred) + ((long)s * (4 + g.nc + g.obb + g.n_extra) + 4) * g.A + a0;
     float best[N];
     int cls[N];
 #pragma unroll
@@ -184,6 +197,8 @@ __device__ inline bool dp_suppresses(const DpBox& j, const DpBox& i, float thres
     return inter / (area_i + area_j - inter) > thres;
 }
 __device__ inline float dp_to_frame(float v, float off, float gain, float hi) { return fminf(fmaxf((v - off) / gain, 0.0f), hi); }
+// ... and of a tiled call: clipped to the tile, then shifted by the tile's origin in the frame (det_post_tiled.hpp step 3b)
+__device__ inline float dp_tile_to_frame(float v, float off, float gain, float hi, float origin) { return fminf(fmaxf((v - off) / gain, 0.0f), hi) + origin; }
 
 // The workgroup's dynamic LDS: the candidate words, a per-candidate table of `tab_bytes` each (the box, or the oriented path's
 // Gaussian), the classes, the fixed part and the suppression flags.
@@ -387,99 +402,22 @@ __device__ inline void dp_finish(const DetPostArgs& g, int s, const DpCount& cnt
     g.counters[s * DP_COUNTERS + 2] = kept;
 }
 
-template <class T>
-__global__ void __launch_bounds__(DP_THREADS) k_detpost_select(DetPostArgs g) {
-    BM_DYNAMIC_LDS_T(unsigned char, lds);
-    const int slots = detpost_slots(g.K);
-    const DpLds m = dp_lds(lds, slots, (int)sizeof(DpBox));
-    const unsigned long long* cand = m.cand;
-    DpBox* box = reinterpret_cast<DpBox*>(m.tab);
-
-    const int s = (int)blockIdx.x, t = (int)threadIdx.x;
-    const T* pred = static_cast<const T*>(g.pred);
-
-    // a-c. the passing count, the exact top-K, the sort
-    const DpCount cnt = dp_select_sort(g, s, m, slots);
-
-    // d. boxes
-    for (int i = t; i < cnt.n_cand; i += DP_THREADS) {
-        const int a = (int)(0xffffffffu - (uint32_t)cand[i]);
-        const float cx = dp_load(pred, dp_at(g, s, a, 0)), cy = dp_load(pred, dp_at(g, s, a, 1)), w = dp_load(pred, dp_at(g, s, a, 2)),
-                    h = dp_load(pred, dp_at(g, s, a, 3));
-        box[i] = DpBox{cx - w * 0.5f, cy - h * 0.5f, cx + w * 0.5f, cy + h * 0.5f};
-        m.ccls[i] = g.cls[(long)s * g.A + a];
-    }
-    __syncthreads();
-
-    // e. NMS and the rows, through to_frame's arithmetic (the stage is explained above dp_finish)
-    const DetPostGeom geo = g.geom[s];
-    float* rows = g.dets + (long)s * g.out_stride * 6;
-    const int n_cand = cnt.n_cand, lane = t & 63, wave = t >> 6;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    int* ccls = m.ccls;
-    unsigned long long* rowm = m.rowm;
-    unsigned char* sup = m.sup;
-    int kept = 0;                   // (the same in every thread)
-    for (int c0 = 0; c0 < n_cand; c0 += DP_CHUNK) {
-        const int i = c0 + lane;
-        const bool valid = i < n_cand;
-        const DpBox mine = valid ? box[i] : DpBox{0.f, 0.f, 0.f, 0.f};
-        const int mcls = valid ? ccls[i] : -1;
-        const unsigned long long live0 = __ballot(valid && !sup[i]);         // what the earlier chunks left alive (every wavefront asks)
-        for (int r = 0; r < DP_CHUNK / (DP_THREADS / 64); ++r) {
-            const int j = wave * (DP_CHUNK / (DP_THREADS / 64)) + r;
-            if (!((live0 >> j) & 1ull) || (live0 >> j) == 1ull) {           // j is gone already, or nobody after it is left: an empty row
-                if (lane == 0) rowm[j] = 0ull;
-                continue;
-            }
-            const DpBox bj = dp_readlane(mine, j);                          // candidate j's box and class out of lane j's registers
-            const int cj = (int)BM_READLANE_U32((unsigned)mcls, j);
-            const bool hit = ((live0 >> lane) & 1ull) && lane > j && (g.agnostic || cj == mcls) && dp_suppresses(bj, mine, g.iou_thres);
-            const unsigned long long hm = __ballot(hit);
-            if (lane == 0) rowm[j] = hm;
-        }
-        __syncthreads();
-        const unsigned long long myrow = rowm[lane];
-        const unsigned mylo = (unsigned)myrow, myhi = (unsigned)(myrow >> 32);
-        unsigned long long km = live0;
-        for (unsigned long long rest = km; rest;) {
-            const int j = __builtin_ctzll(rest);
-            km &= ~(((unsigned long long)BM_READLANE_U32(myhi, j) << 32) | (unsigned long long)BM_READLANE_U32(mylo, j));
-            rest = j == 63 ? 0ull : km & ~((2ull << j) - 1ull);
-        }
-        if (wave == 0) {
-            const bool alive = (km >> lane) & 1ull;
-            const int rank = kept + __popcll(km & below);
-            if (alive && rank < g.max_det) {
-                float* r = rows + (long)rank * 6;
-                r[0] = dp_to_frame(mine.x1, geo.left, geo.gain, geo.cols);
-                r[1] = dp_to_frame(mine.y1, geo.top, geo.gain, geo.rows);
-                r[2] = dp_to_frame(mine.x2, geo.left, geo.gain, geo.cols);
-                r[3] = dp_to_frame(mine.y2, geo.top, geo.gain, geo.rows);
-                r[4] = __uint_as_float((uint32_t)(cand[i] >> 32));
-                r[5] = (float)mcls;
-            }
-        }
-        kept += __popcll(km);
-        if (km && c0 + DP_CHUNK < n_cand) {
-            for (int q = c0 + DP_CHUNK + t; q < n_cand; q += DP_THREADS) {
-                if (sup[q]) continue;
-                const DpBox qb = box[q];
-                const int qcls = ccls[q];
-                for (unsigned long long mm = km; mm; mm &= mm - 1ull) {
-                    const int j = c0 + __builtin_ctzll(mm);
-                    if ((g.agnostic || ccls[j] == qcls) && dp_suppresses(box[j], qb, g.iou_thres)) { sup[q] = 1; break; }
-                }
-            }
-        }
-        __syncthreads();
-    }
-    dp_finish(g, s, cnt, kept);
-}
+// k_detpost_select (heads without extras) and k_detpost_select_src (with: det_post_extra.hpp) are one text, det_post_select_body.hpp
+#define DP_SELECT_KERNEL k_detpost_select
+#define DP_SELECT_SRC false
+#include "det_post_select_body.hpp"
+#undef DP_SELECT_KERNEL
+#undef DP_SELECT_SRC
+#define DP_SELECT_KERNEL k_detpost_select_src
+#define DP_SELECT_SRC true
+#include "det_post_select_body.hpp"
+#undef DP_SELECT_KERNEL
+#undef DP_SELECT_SRC
 
 }  // namespace bm
 
 #include "det_post_obb.hpp"         // the oriented layout: k_detpost_select_obb
+#include "det_post_extra.hpp"       // per-anchor extras: k_detpost_extra
 
 namespace bm {
 
@@ -499,7 +437,16 @@ inline void detpost_launch_score(L& launch, const DetPostArgs& g, int n_tensors,
     }
 }
 
-// The kernel sequence of one call.
+// The third kernel of a call on a head with extras (g.n_extra > 0: g.src and g.extra must be set; tgeom / n_tiles of a tiled call, else
+// null / 0).
+template <class L>
+inline void detpost_launch_extra(L& launch, const DetPostArgs& g, const DetPostTileGeom* tgeom, int n_tiles, int n_streams, int fp16) {
+    const int gx = detpost_extra_grid_x(g.max_det, g.n_extra);
+    if (fp16) launch(k_detpost_extra<_Float16>, gx, n_streams, DP_EXTRA_THREADS, (size_t)0, g, tgeom, n_tiles);
+    else launch(k_detpost_extra<float>, gx, n_streams, DP_EXTRA_THREADS, (size_t)0, g, tgeom, n_tiles);
+}
+
+// The kernel sequence of one call.  (The oriented layout has no extras: the library refuses the combination.)
 template <class L>
 inline void detpost_launch(L& launch, const DetPostArgs& g, int n_streams, int fp16, size_t* lds_bytes = nullptr) {
     const size_t lds = g.obb ? detpost_obb_lds_bytes(g.K) : detpost_lds_bytes(g.K);
@@ -507,11 +454,14 @@ inline void detpost_launch(L& launch, const DetPostArgs& g, int n_streams, int f
     detpost_launch_score(launch, g, n_streams, fp16);
     if (fp16) {
         if (g.obb) launch(k_detpost_select_obb<_Float16>, n_streams, 1, DP_THREADS, lds, g);
+        else if (g.n_extra > 0) launch(k_detpost_select_src<_Float16>, n_streams, 1, DP_THREADS, lds, g);
         else launch(k_detpost_select<_Float16>, n_streams, 1, DP_THREADS, lds, g);
     } else {
         if (g.obb) launch(k_detpost_select_obb<float>, n_streams, 1, DP_THREADS, lds, g);
+        else if (g.n_extra > 0) launch(k_detpost_select_src<float>, n_streams, 1, DP_THREADS, lds, g);
         else launch(k_detpost_select<float>, n_streams, 1, DP_THREADS, lds, g);
     }
+    if (g.n_extra > 0 && !g.obb) detpost_launch_extra(launch, g, nullptr, 0, n_streams, fp16);
 }
 
 }  // namespace bm

@@ -35,6 +35,22 @@ ascending) are mapped to the frame -- ``clip((x - left) / gain, 0, w) + x0`` -- 
 ``merge="iou"`` suppresses on ``IoU > iou``, ``merge="ios"`` on ``inter / min(area_i, area_j) > iou`` (intersection over the
 smaller box: a box cut by a tile's edge is absorbed by the whole one).  It is pinned against this repository's NumPy restatement
 (tests/detpost_tiled_ref.py) only, not against SAHI or Ultralytics.
+
+Pose and segmentation heads: ``DetPost(..., extra=E, extra_kind="raw" | "kpt2" | "kpt3")`` reads heads with ``E`` more values per
+anchor after the class scores -- (S, 4 + n_classes + E, n_anchors) for ``"cn"``, (S, n_anchors, 5 + n_classes + E) for ``"nc_obj"``
+-- and writes, beside the rows and in their order, the anchor each row came from and that anchor's extras (the definition is at
+the top of csrc/det_post_extra.hpp); the tracker's ``det_ind`` column then finds the skeleton or the mask coefficients of a track:
+
+    post = DetPost(S, n_anchors=8400, n_classes=1, layout="cn", extra=51, extra_kind="kpt3", max_det=256)   # "raw" for -seg coefficients
+    d_kpts = torch.empty((S, 256, 51), device="cuda"); d_src = torch.empty((S, 256), dtype=torch.int32, device="cuda")
+    post.run(pose_model(x), geo, d_dets, d_rows, hip_stream=st, d_extra=d_kpts, d_src=d_src)               # d_src optional
+    trk.step_device(d_dets.data_ptr(), d_rows.data_ptr(), ...)
+    kpts_of_tracks = d_kpts[s][d_out[s, :n_out, 7].long()]           # det_ind -> the skeleton of each track
+
+Stated plainly: ``"kpt2"`` / ``"kpt3"`` map x and y to the frame with the arithmetic of the boxes, ``clip((v - left) / gain, 0, cols)``
+(tiled: the row's own tile, clipped to it, then shifted), and copy the visibility; ``"raw"`` copies.  A NaN coordinate comes out as 0.
+This is a reading of Ultralytics' ``scale_coords`` + ``clip_coords``, pinned against this repository's NumPy restatement
+(tests/detpost_extra_ref.py) only.  Mask decoding (coefficients x prototypes) stays the caller's.  Not for ``"cn_obb"``.
 """
 from __future__ import annotations
 
@@ -48,6 +64,8 @@ LAYOUTS = {"cn": 0, "nc_obj": 1, "cn_obb": 0}          # the C ABI's layout code
 NMS_MODES = {"greedy": 0, "fast": 1}
 MERGES = {"iou": 0, "ios": 1}
 MAX_TILES = 64
+EXTRA_KINDS = {"raw": 0, "kpt2": 1, "kpt3": 2}
+MAX_EXTRA = 1024
 _DTYPES = {"float32": 0, "float16": 1}
 
 
@@ -88,7 +106,8 @@ def _tile_geometry_row(g, s, t):
 class DetPost:
     def __init__(self, n_streams: int, n_anchors: int, n_classes: int, layout: str = "cn", conf: float = 0.25, iou: float = 0.45,
                  max_det: int = 256, max_candidates: int = 1024, agnostic: bool = False, classes=None, nms: str | None = None,
-                 regularize: bool | None = None, tiles: int | None = None, merge: str | None = None):
+                 regularize: bool | None = None, tiles: int | None = None, merge: str | None = None, extra: int | None = None,
+                 extra_kind: str | None = None):
         """``layout``: ``"cn"`` -- (S, 4 + n_classes, n_anchors), the Ultralytics v8 / 11 raw head, conf = the best class score --
         ``"nc_obj"`` -- (S, n_anchors, 5 + n_classes), the YOLOX / YOLOv5 decoded head, conf = obj * the best class score -- or
         ``"cn_obb"`` -- (S, 4 + n_classes + 1, n_anchors), the Ultralytics OBB raw head, the angle in radians as the last row.
@@ -96,9 +115,13 @@ class DetPost:
         default, or ``"fast"``) and ``regularize`` (w >= h and the angle within [0, pi] in the rows; default off) belong to
         ``"cn_obb"`` alone.  ``tiles``: the detector ran on that many tiles per stream (``FrameRing.letterbox_tiles``) and their
         detections are merged by one NMS per stream in frame coordinates, on ``merge="iou"`` (the default) or ``"ios"``,
-        intersection over the smaller box; ``n_anchors`` stays the anchors of ONE tile tensor.  Not for ``"cn_obb"``."""
+        intersection over the smaller box; ``n_anchors`` stays the anchors of ONE tile tensor.  Not for ``"cn_obb"``.
+        ``extra``: the head has that many more values per anchor after the class scores (1..1024) and ``run`` also writes
+        ``d_extra`` / ``d_src``; ``extra_kind``: ``"raw"`` (the default) copies them, ``"kpt2"`` / ``"kpt3"`` map keypoints (x, y /
+        x, y, visibility) to the frame.  With ``tiles`` or without; not for ``"cn_obb"``."""
         self._handle = None
-        self._configure(n_streams, n_anchors, n_classes, layout, conf, iou, max_det, max_candidates, agnostic, classes, nms, regularize, tiles, merge)
+        self._configure(n_streams, n_anchors, n_classes, layout, conf, iou, max_det, max_candidates, agnostic, classes, nms, regularize, tiles, merge,
+                        extra, extra_kind)
         self._lib = _lib.load()
         allow = None
         if self.classes is not None:
@@ -106,7 +129,10 @@ class DetPost:
             allow[self.classes] = 1
         cfg = _lib.DetPostConfig(self.n_streams, self.n_anchors, self.n_classes, LAYOUTS[self.layout], self.conf, self.iou, self.max_candidates,
                                  self.max_det, int(self.agnostic), None if allow is None else allow.ctypes.data)
-        if self.tiles is not None:
+        if self.extra is not None:
+            ecfg = _lib.DetPostExtraConfig(cfg, self.tiles or 0, MERGES[self.merge or "iou"], self.extra, EXTRA_KINDS[self.extra_kind])
+            self._handle = self._lib.boxmot_hip_detpost_create_extra(ctypes.byref(ecfg))
+        elif self.tiles is not None:
             tcfg = _lib.DetPostTiledConfig(cfg, self.tiles, MERGES[self.merge])
             self._handle = self._lib.boxmot_hip_detpost_create_tiled(ctypes.byref(tcfg))
         elif self.is_obb:
@@ -118,7 +144,7 @@ class DetPost:
             raise RuntimeError(_lib.last_error())
 
     def _configure(self, n_streams, n_anchors, n_classes, layout="cn", conf=0.25, iou=0.45, max_det=256, max_candidates=1024, agnostic=False,
-                   classes=None, nms=None, regularize=None, tiles=None, merge=None):
+                   classes=None, nms=None, regularize=None, tiles=None, merge=None, extra=None, extra_kind=None):
         """the options, checked; touches neither the library nor a device"""
         for name, v in (("n_streams", n_streams), ("n_anchors", n_anchors), ("n_classes", n_classes), ("max_det", max_det)):
             if int(v) != v or int(v) < 1:
@@ -138,6 +164,19 @@ class DetPost:
             merge = "iou" if merge is None else merge
             if merge not in MERGES:
                 raise ValueError(f"DetPost: unknown merge {merge!r} (\"iou\" or \"ios\")")
+        if extra is None and extra_kind is not None:
+            raise ValueError("DetPost: extra_kind= belongs to a head with extras: give extra= as well")
+        if extra is not None:
+            if is_obb:
+                raise ValueError("DetPost: layout \"cn_obb\" has no extras: extra= is for \"cn\" and \"nc_obj\"")
+            if int(extra) != extra or not 1 <= int(extra) <= MAX_EXTRA:
+                raise ValueError(f"DetPost: extra must be an integer within 1..{MAX_EXTRA}, got {extra!r}")
+            extra_kind = "raw" if extra_kind is None else extra_kind
+            if extra_kind not in EXTRA_KINDS:
+                raise ValueError(f"DetPost: unknown extra_kind {extra_kind!r} (\"raw\", \"kpt2\" or \"kpt3\")")
+            group = {"raw": 1, "kpt2": 2, "kpt3": 3}[extra_kind]
+            if int(extra) % group:
+                raise ValueError(f"DetPost: extra_kind {extra_kind!r} takes values in groups of {group}: extra = {extra} is no multiple")
         nms = "greedy" if nms is None else nms
         if nms not in NMS_MODES:
             raise ValueError(f"DetPost: unknown nms {nms!r} (\"greedy\" or \"fast\")")
@@ -156,7 +195,8 @@ class DetPost:
         self.conf, self.iou = float(np.float32(conf)), float(np.float32(iou))          # the thresholds are float32 on the device
         self.max_det, self.max_candidates, self.agnostic, self.classes = int(max_det), int(max_candidates), bool(agnostic), classes
         self.is_obb, self.nms, self.regularize = is_obb, nms if is_obb else None, bool(regularize) if is_obb else None
-        self.n_channels = 5 + self.n_classes if is_obb or layout == "nc_obj" else 4 + self.n_classes       # per anchor, in the layout
+        self.extra, self.extra_kind = (None, None) if extra is None else (int(extra), extra_kind)
+        self.n_channels = (5 + self.n_classes if is_obb or layout == "nc_obj" else 4 + self.n_classes) + (self.extra or 0)    # per anchor, in the layout
         self.det_cols = 7 if is_obb else 6
         self.tiles, self.merge = (None, None) if tiles is None else (int(tiles), merge)
 
@@ -164,7 +204,7 @@ class DetPost:
         n = (self.n_streams if n is None else n) * (self.tiles or 1)
         return (n, self.n_anchors, self.n_channels) if self.layout == "nc_obj" else (n, self.n_channels, self.n_anchors)
 
-    def _check_run(self, pred, geo, d_dets, d_det_rows):
+    def _check_run(self, pred, geo, d_dets, d_det_rows, d_extra=None, d_src=None):
         """(n_streams, dtype code, geometry table) of a call; raises ValueError naming what is wrong"""
         n = len(geo)
         if not 1 <= n <= self.n_streams:
@@ -198,7 +238,31 @@ class DetPost:
             raise ValueError(f"DetPost.run: d_det_rows must be int32, got {d_det_rows.dtype}")
         if not d_det_rows.is_contiguous():
             raise ValueError("DetPost.run: d_det_rows must be contiguous")
-        for name, t in (("pred", pred), ("d_dets", d_dets), ("d_det_rows", d_det_rows)):
+        out = [("pred", pred), ("d_dets", d_dets), ("d_det_rows", d_det_rows)]
+        if self.extra is None:
+            if d_extra is not None or d_src is not None:
+                raise ValueError("DetPost.run: d_extra and d_src belong to a handle with extras (extra=), which this one is not")
+        else:
+            if d_extra is None:
+                raise ValueError(f"DetPost.run: a handle of extra={self.extra} needs d_extra")
+            eshape = tuple(int(v) for v in d_extra.shape)
+            if len(eshape) != 3 or eshape[0] < n or eshape[1] != dshape[1] or eshape[2] != self.extra:
+                raise ValueError(f"DetPost.run: d_extra must have shape (N >= {n}, {dshape[1]}, {self.extra}), the rows of d_dets, got {eshape}")
+            if _dtype_name(d_extra) != "float32":
+                raise ValueError(f"DetPost.run: d_extra must be float32, got {d_extra.dtype}")
+            if not d_extra.is_contiguous():
+                raise ValueError("DetPost.run: d_extra must be contiguous")
+            out.append(("d_extra", d_extra))
+            if d_src is not None:
+                sshape = tuple(int(v) for v in d_src.shape)
+                if len(sshape) != 2 or sshape[0] < n or sshape[1] != dshape[1]:
+                    raise ValueError(f"DetPost.run: d_src must have shape (N >= {n}, {dshape[1]}), the rows of d_dets, got {sshape}")
+                if _dtype_name(d_src) != "int32":
+                    raise ValueError(f"DetPost.run: d_src must be int32, got {d_src.dtype}")
+                if not d_src.is_contiguous():
+                    raise ValueError("DetPost.run: d_src must be contiguous")
+                out.append(("d_src", d_src))
+        for name, t in out:
             if not int(t.data_ptr()):
                 raise ValueError(f"DetPost.run: {name} has a null device address")
         if self.tiles is not None:
@@ -207,7 +271,7 @@ class DetPost:
             table = np.array([_geometry_row(g, s) for s, g in enumerate(geo)], dtype=np.float64)
         return n, dtype, table, dshape[1]
 
-    def run(self, pred, geo, d_dets, d_det_rows, hip_stream: int = 0) -> None:
+    def run(self, pred, geo, d_dets, d_det_rows, hip_stream: int = 0, d_extra=None, d_src=None) -> None:
         """``pred``: the detector's raw output of the first ``len(geo)`` streams, a contiguous float16 / float32 device tensor in
         the handle's layout -- anything with ``data_ptr()``, ``dtype``, ``shape`` and ``is_contiguous()``; ``geo``: what
         ``FrameRing.letterbox`` returned for them; ``d_dets``: (N, rows >= max_det, 6) float32, ``d_det_rows``: (N,) int32, on the
@@ -215,8 +279,17 @@ class DetPost:
         stream; rows at and beyond the count, and streams beyond ``len(geo)``, are left alone.  Layout ``"cn_obb"``: ``d_dets`` is
         (N, rows >= max_det, 7), rows ``[cx, cy, w, h, angle, conf, cls]``, not clipped to the frame.  A handle of ``tiles=T``:
         ``pred`` holds ``len(geo) * T`` tensors and ``geo`` is what ``FrameRing.letterbox_tiles`` returned, per stream a list of
-        ``T`` ``TileGeometry`` (or 7-sequences gain, top, left, x0, y0, w, h); ``d_dets`` / ``d_det_rows`` stay per stream."""
-        n, dtype, table, stride = self._check_run(pred, geo, d_dets, d_det_rows)
+        ``T`` ``TileGeometry`` (or 7-sequences gain, top, left, x0, y0, w, h); ``d_dets`` / ``d_det_rows`` stay per stream.
+        A handle of ``extra=E``: ``d_extra`` (N, rows of d_dets, E) float32 takes the extras of every row and, where given,
+        ``d_src`` (N, rows of d_dets) int32 the anchor it came from (tiled: ``t * n_anchors + a``); rows beyond the count are left
+        alone there too."""
+        n, dtype, table, stride = self._check_run(pred, geo, d_dets, d_det_rows, d_extra, d_src)
+        if self.extra is not None:
+            _lib.check(self._lib.boxmot_hip_detpost_run_extra(
+                self._handle, n, ctypes.c_void_p(int(pred.data_ptr())), dtype, table.ctypes.data_as(_lib.c_double_p),
+                ctypes.c_void_p(int(d_dets.data_ptr())), stride, ctypes.c_void_p(int(d_det_rows.data_ptr())), ctypes.c_void_p(int(d_extra.data_ptr())),
+                None if d_src is None else ctypes.c_void_p(int(d_src.data_ptr())), ctypes.c_void_p(int(hip_stream))))
+            return
         run = self._lib.boxmot_hip_detpost_run if self.tiles is None else self._lib.boxmot_hip_detpost_run_tiled
         _lib.check(run(self._handle, n, ctypes.c_void_p(int(pred.data_ptr())), dtype,
                        table.ctypes.data_as(_lib.c_double_p), ctypes.c_void_p(int(d_dets.data_ptr())), stride,
@@ -224,7 +297,8 @@ class DetPost:
 
     def run_host(self, pred, geo) -> list:
         """Convenience form: ``pred`` a device tensor or a host array (uploaded); returns the rows of each stream as an (n_s, 6)
-        float32 array, (n_s, 7) for layout ``"cn_obb"``.  Allocates its outputs with torch and waits for the result."""
+        float32 array, (n_s, 7) for layout ``"cn_obb"``; on a handle of ``extra=E`` a tuple ``(rows, extras (n_s, E) float32, src (n_s,)
+        int32)`` per stream.  Allocates its outputs with torch and waits for the result."""
         import torch
         if isinstance(pred, np.ndarray):
             pred = torch.from_numpy(np.ascontiguousarray(pred)).cuda()
@@ -232,10 +306,17 @@ class DetPost:
         d_dets = torch.empty((max(n, 1), self.max_det, self.det_cols), dtype=torch.float32, device=pred.device)
         d_rows = torch.zeros(max(n, 1), dtype=torch.int32, device=pred.device)
         st = torch.cuda.current_stream(pred.device)
-        self.run(pred, geo, d_dets, d_rows, hip_stream=st.cuda_stream)
+        if self.extra is None:
+            self.run(pred, geo, d_dets, d_rows, hip_stream=st.cuda_stream)
+            st.synchronize()
+            rows, dets = d_rows.cpu().numpy(), d_dets.cpu().numpy()
+            return [dets[s, :rows[s]].copy() for s in range(n)]
+        d_extra = torch.empty((max(n, 1), self.max_det, self.extra), dtype=torch.float32, device=pred.device)
+        d_src = torch.empty((max(n, 1), self.max_det), dtype=torch.int32, device=pred.device)
+        self.run(pred, geo, d_dets, d_rows, hip_stream=st.cuda_stream, d_extra=d_extra, d_src=d_src)
         st.synchronize()
-        rows, dets = d_rows.cpu().numpy(), d_dets.cpu().numpy()
-        return [dets[s, :rows[s]].copy() for s in range(n)]
+        rows, dets, extras, src = d_rows.cpu().numpy(), d_dets.cpu().numpy(), d_extra.cpu().numpy(), d_src.cpu().numpy()
+        return [(dets[s, :rows[s]].copy(), extras[s, :rows[s]].copy(), src[s, :rows[s]].copy()) for s in range(n)]
 
     def counters(self) -> np.ndarray:
         """(n_streams, 3) int32 of the last run, after waiting for it: anchors that passed the threshold, candidates after the

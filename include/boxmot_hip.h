@@ -468,6 +468,29 @@ BoxMOTHipDetPost* boxmot_hip_detpost_create_tiled(const BoxMOTHipDetPostTiledCon
 int boxmot_hip_detpost_run_tiled(BoxMOTHipDetPost* handle, int n_streams, const void* d_pred, int dtype, const double* geom, float* d_dets,
                                  int out_stride_rows, int* d_det_rows, void* hip_stream);
 
+/* Heads with per-anchor extras (csrc/det_post_extra.hpp has the full definition): pose heads (Ultralytics *-pose, 17 x 3 keypoint
+ * values after the class scores) and segmentation heads (*-seg, 32 mask coefficients) carry n_extra (1..1024) more values per
+ * anchor: layout 0 is (S, 4 + n_classes + n_extra, n_anchors), layout 1 (S, n_anchors, 5 + n_classes + n_extra).  Everything above
+ * runs unchanged and reads none of them; beside the rows, and in their order, run_extra writes d_src [n][out_stride_rows] int32, the
+ * anchor every row came from (tiled: t * n_anchors + a), and d_extra [n][out_stride_rows][n_extra] fp32, that anchor's extras:
+ * extra_kind 0 "raw" as they are; 1 "kpt2" / 2 "kpt3" in groups of 2 / 3 (n_extra a multiple), x and y through the arithmetic of
+ * the boxes -- min(max((v - left) / gain, 0), cols), likewise y with top and rows; tiled: the row's own tile, clipped to it and
+ * shifted by x0 / y0 -- the third value (visibility) copied.  A NaN coordinate comes out as 0 (tiled: x0 / y0).  Rows at and
+ * beyond d_det_rows[s] are not touched in either block.  n_tiles 0: an untiled handle, geom [n_streams][5]; n_tiles 1..64: a
+ * tiled one, merge and geom [n_streams][n_tiles][7] as above.  d_src may be null (the handle keeps the anchors in a scratch of its
+ * own); d_extra may not.  Such a handle is run with run_extra only -- boxmot_hip_detpost_run / _run_tiled refuse it, as run_extra
+ * refuses a handle without extras -- and read and destroyed with boxmot_hip_detpost_counters / _destroy.  The oriented layout has
+ * no extras. */
+typedef struct BoxMOTHipDetPostExtraConfig {
+    BoxMOTHipDetPostConfig base;
+    int n_tiles, merge;              /* n_tiles 0: untiled */
+    int n_extra;                     /* 1..1024 */
+    int extra_kind;                  /* 0 raw, 1 kpt2, 2 kpt3 */
+} BoxMOTHipDetPostExtraConfig;
+BoxMOTHipDetPost* boxmot_hip_detpost_create_extra(const BoxMOTHipDetPostExtraConfig* config);
+int boxmot_hip_detpost_run_extra(BoxMOTHipDetPost* handle, int n_streams, const void* d_pred, int dtype, const double* geom, float* d_dets,
+                                 int out_stride_rows, int* d_det_rows, float* d_extra, int* d_src /* may be null */, void* hip_stream);
+
 /* ------------------------------------------------------------------------------------------------
  * DeepOCSORT (boxmot/trackers/bbox/deepocsort/deepocsort.py:235-492).  The reference has no native backend
  * for this tracker; the entry points follow the BoT-SORT ones above (same buffer, error and ownership

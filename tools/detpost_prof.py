@@ -12,7 +12,14 @@ streams, a sparse and a busy scene; per scene the axis-aligned path on the same 
 oriented path in both NMS modes, from the same run.  The checksums are compared with tests/detpost_obb_ref.py; where a scene has a
 pair within the reference's margin of the threshold the NMS decisions may differ, which is reported and not an error.
 
-Needs a gfx950 device.  profiles/detpost_timing.txt and profiles/detpost_obb_timing.txt are the outputs of one such run each."""
+``--extra`` times a POSE head instead (csrc/det_post_extra.hpp): A = 8400 anchors, 1 class, E = 51 values per anchor ("kpt3": 17
+keypoints), fp16, "cn", 64 streams, a quiet and a busy scene; the three-kernel sequence -- score, the select kernel's source-storing
+variant, k_detpost_extra -- with the third kernel's useful bytes per second (what it has to read and write: per emitted value one
+element of the tensor and one float32, per row one source index), beside the host path it replaces, the copy of the tensor plus
+tests/detpost_extra_ref.py on this host.  The checksum covers the rows, the extras and the source anchors.
+
+Needs a gfx950 device.  profiles/detpost_timing.txt, profiles/detpost_obb_timing.txt and profiles/detpost_extra_timing.txt hold the
+outputs of such runs."""
 import argparse
 import os
 import subprocess
@@ -27,7 +34,7 @@ ROOT = Path(__file__).resolve().parent.parent
 SRC = ROOT / "tools" / "detpost_prof.hip"
 EXE = ROOT / "tools" / "_build" / "detpost_prof"
 CSRC = ROOT / "boxmot_amd" / "csrc"
-DEPS = [SRC, CSRC / "det_post.hpp", CSRC / "det_post_obb.hpp", CSRC / "kernel_macros.hpp"]
+DEPS = [SRC, CSRC / "det_post.hpp", CSRC / "det_post_obb.hpp", CSRC / "det_post_extra.hpp", CSRC / "det_post_select_body.hpp", CSRC / "kernel_macros.hpp"]
 sys.path[:0] = [str(ROOT / "tests"), str(ROOT)]          # the reference lives with the tests
 
 
@@ -107,6 +114,40 @@ def main_obb(exe, a, out) -> int:
     return 0
 
 
+def main_extra(exe, a, out) -> int:
+    import detpost_extra_ref as eref
+    import detpost_ref as ref
+    A, nc, E, kind, K, max_det, S = 8400, 1, 51, "kpt3", 1024, 256, 64
+    geo = ref.GEO_CENTER
+    for name, rate in (("quiet", 0.01), ("busy", 0.3)):
+        pred = eref.with_extras(ref.random_pred(A, nc, "cn", np.float16, 1, rate, n_obj=60), "cn", eref.make_extras(A, E, kind, 2), np.float16)
+        path = out / f"detpost_extra_pred_{name}.bin"
+        pred.tofile(path)
+        times = []
+        for _ in range(5):
+            t0 = time.perf_counter()
+            rows, counters, extras, src = eref.detpost_extra(pred, geo, "cn", nc, E, kind, 0.25, 0.45, max_det, K)
+            times.append(time.perf_counter() - t0)
+        want = checksum(rows, counters) + f" extra {float(extras.astype(np.float64).sum()):.6f} src {int(src.astype(np.int64).sum())}"
+        print(f"== {name} scene (pass rate {rate}): {counters[0]} of {A} anchors pass, {counters[1]} candidates, {counters[2]} kept by NMS, {len(rows)} rows", flush=True)
+        print(f"NumPy reference of ONE stream on this host (tests/detpost_extra_ref.py): median {1e3 * sorted(times)[2]:.2f} ms of 5", flush=True)
+        r = subprocess.run([str(exe), str(path), *[str(v) for v in (S, A, nc, 0, 1, K, max_det, a.repeats, 0, 0, E, eref.KINDS[kind])]], capture_output=True,
+                           text=True, timeout=300)
+        print(r.stdout, end="", flush=True)
+        if r.returncode != 0:
+            print(r.stderr, file=sys.stderr)
+            return r.returncode or 1
+        got = [ln for ln in r.stdout.splitlines() if ln.startswith("checksum:")][0]
+        if got != want:
+            print(f"CHECKSUM MISMATCH: device `{got}`, reference `{want}`", file=sys.stderr)
+            return 1
+        print("checksum equals the reference's", flush=True)
+        med = [float(ln.split("median")[1].split("us")[0]) for ln in r.stdout.splitlines() if ln.startswith("k_detpost_extra")][0]
+        useful = S * len(rows) * (E * (pred.itemsize + 4) + 4)
+        print(f"k_detpost_extra: {useful} useful bytes ({S} x {len(rows)} rows x {E} values) in {med:.1f} us: {useful / med * 1e-3:.2f} GB/s", flush=True)
+    return 0
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--streams", type=int, nargs="+", default=[1, 16, 64])
@@ -115,10 +156,15 @@ def main() -> int:
     ap.add_argument("--out", default=None, help="directory for the tensor files (default: a temporary one)")
     ap.add_argument("--build-only", action="store_true", help="compile the measuring program and stop (no device needed)")
     ap.add_argument("--obb", action="store_true", help="the oriented layout beside the axis-aligned one at 64 x 21504 x 15 (see above)")
+    ap.add_argument("--extra", action="store_true", help="a pose head, 64 x 8400 x (4 + 1 + 51): the three-kernel sequence with extras (see above)")
     a = ap.parse_args()
     exe = build()
     if a.build_only:
         return 0
+    if a.extra:
+        out = Path(a.out) if a.out else Path(tempfile.mkdtemp())
+        out.mkdir(parents=True, exist_ok=True)
+        return main_extra(exe, a, out)
     if a.obb:
         out = Path(a.out) if a.out else Path(tempfile.mkdtemp())
         out.mkdir(parents=True, exist_ok=True)
