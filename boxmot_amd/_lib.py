@@ -135,6 +135,12 @@ class DetPostExtraConfig(ctypes.Structure):
     _fields_ = [("base", DetPostConfig), ("n_tiles", ctypes.c_int), ("merge", ctypes.c_int), ("n_extra", ctypes.c_int), ("extra_kind", ctypes.c_int)]
 
 
+class DetPostMaskConfig(ctypes.Structure):
+    """``BoxMOTHipDetPostMaskConfig`` (include/boxmot_hip.h)."""
+
+    _fields_ = [("extra", DetPostExtraConfig), ("mask_h", ctypes.c_int), ("mask_w", ctypes.c_int), ("in_h", ctypes.c_int), ("in_w", ctypes.c_int)]
+
+
 class Letterbox(ctypes.Structure):
     """``BoxMOTHipLetterbox`` (include/boxmot_hip.h)."""
 
@@ -271,6 +277,8 @@ SIGNATURES = {
     "boxmot_hip_detpost_run_tiled": (_I, [_VP, _I, _VP, _I, c_double_p, _VP, _I, _VP, _VP]),
     "boxmot_hip_detpost_create_extra": (_VP, [ctypes.POINTER(DetPostExtraConfig)]),
     "boxmot_hip_detpost_run_extra": (_I, [_VP, _I, _VP, _I, c_double_p, _VP, _I, _VP, _VP, _VP, _VP]),
+    "boxmot_hip_detpost_create_mask": (_VP, [ctypes.POINTER(DetPostMaskConfig)]),
+    "boxmot_hip_detpost_run_mask": (_I, [_VP, _I, _VP, _I, c_double_p, _VP, _I, _VP, _VP, _VP, _VP, _I, _VP, _VP]),
     "boxmot_hip_last_error": (ctypes.c_char_p, []),
     "boxmot_hip_device_count": (_I, []),
     "boxmot_hip_botsort_device": (_I, [_VP]),

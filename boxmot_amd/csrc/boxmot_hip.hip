@@ -28,6 +28,7 @@
 #include "ingest_letterbox_tiles.hpp"
 #include "det_post.hpp"
 #include "det_post_tiled.hpp"
+#include "det_post_mask.hpp"
 
 namespace {
 
@@ -399,6 +400,9 @@ struct BoxMOTHipDetPost : DeviceBound {
     // a handle with per-anchor extras (boxmot_hip_detpost_create_extra, csrc/det_post_extra.hpp), tiled or not
     int n_extra = 0, extra_kind = 0;
     int* d_src = nullptr;                           // [n_streams][max_det]: where the source anchors go when the caller gives no d_src
+    // a mask handle (boxmot_hip_detpost_create_mask, csrc/det_post_mask.hpp): an extras handle of kind "raw" with these; mask_h 0: none
+    int mask_h = 0, mask_w = 0;
+    float mask_wr = 0.0f, mask_hr = 0.0f;           // (float)mask_w / (float)in_w, (float)mask_h / (float)in_h
     ~BoxMOTHipDetPost() {
         if (done) { if (ran) (void)hipEventSynchronize(done); (void)hipEventDestroy(done); }
         if (d_src) (void)hipFree(d_src);
@@ -3191,9 +3195,9 @@ int boxmot_hip_ingest_letterbox_tiles(BoxMOTHipIngest* handle, int slot, int n_s
 // ---- detection post-processing (csrc/det_post.hpp has the definition) ----
 namespace {
 // the create entry points; oc: the oriented options, or null for an axis-aligned handle; tc: the tiled options, or null; ec: the
-// per-anchor extras (with tc made of its n_tiles and merge when tiled), or null
+// per-anchor extras (with tc made of its n_tiles and merge when tiled), or null; mc: the mask options (with ec its extras), or null
 BoxMOTHipDetPost* detpost_create(const BoxMOTHipDetPostConfig* c, const BoxMOTHipDetPostObbConfig* oc, const BoxMOTHipDetPostTiledConfig* tc = nullptr,
-                                 const BoxMOTHipDetPostExtraConfig* ec = nullptr) {
+                                 const BoxMOTHipDetPostExtraConfig* ec = nullptr, const BoxMOTHipDetPostMaskConfig* mc = nullptr) {
     BoxMOTHipDetPost* h = nullptr;
     const int ok = guard([&]() {
         if (!c) throw std::runtime_error("boxmot_hip: null detpost config");
@@ -3204,6 +3208,15 @@ BoxMOTHipDetPost* detpost_create(const BoxMOTHipDetPostConfig* c, const BoxMOTHi
         if (ec && ec->n_extra % bm::detpost_extra_group(ec->extra_kind))
             throw std::runtime_error("boxmot_hip: detpost n_extra " + std::to_string(ec->n_extra) + " is no multiple of the " +
                                      std::to_string(bm::detpost_extra_group(ec->extra_kind)) + " values per keypoint of extra_kind " + std::to_string(ec->extra_kind));
+        if (mc && ec->extra_kind != 0)
+            throw std::runtime_error("boxmot_hip: a detpost mask handle needs extra_kind 0 (raw), got " + std::to_string(ec->extra_kind));
+        if (mc && ec->n_extra > bm::DP_MASK_E_MAX)
+            throw std::runtime_error("boxmot_hip: a detpost mask handle needs n_extra within 1.." + std::to_string(bm::DP_MASK_E_MAX) + ", got " + std::to_string(ec->n_extra));
+        if (mc && (mc->mask_h < 1 || mc->mask_h > bm::DP_MASK_DIM_MAX || mc->mask_w < 1 || mc->mask_w > bm::DP_MASK_DIM_MAX))
+            throw std::runtime_error("boxmot_hip: detpost mask_h and mask_w must be within 1.." + std::to_string(bm::DP_MASK_DIM_MAX) + ", got " +
+                                     std::to_string(mc->mask_h) + " x " + std::to_string(mc->mask_w));
+        if (mc && (mc->in_h < 1 || mc->in_w < 1))
+            throw std::runtime_error("boxmot_hip: detpost in_h and in_w must be >= 1, got " + std::to_string(mc->in_h) + " x " + std::to_string(mc->in_w));
         if (oc && c->layout != 0)
             throw std::runtime_error("boxmot_hip: an oriented detpost handle needs base.layout 0 (cn), got " + std::to_string(c->layout));
         if (oc && oc->nms_mode != 0 && oc->nms_mode != 1)
@@ -3232,6 +3245,10 @@ BoxMOTHipDetPost* detpost_create(const BoxMOTHipDetPostConfig* c, const BoxMOTHi
         if (oc) { h->obb = 1; h->nms_mode = oc->nms_mode; h->regularize = oc->regularize ? 1 : 0; }
         if (tc) { h->n_tiles = tc->n_tiles; h->merge = tc->merge; }
         if (ec) { h->n_extra = ec->n_extra; h->extra_kind = ec->extra_kind; }
+        if (mc) {
+            h->mask_h = mc->mask_h; h->mask_w = mc->mask_w;
+            h->mask_wr = (float)mc->mask_w / (float)mc->in_w; h->mask_hr = (float)mc->mask_h / (float)mc->in_h;
+        }
         const size_t SA = (size_t)c->n_streams * n_tensors * c->n_anchors;
         void* p = nullptr;
         BM_HIP(hipMalloc(&p, SA * sizeof(uint32_t))); h->d_keys = static_cast<uint32_t*>(p);
@@ -3299,6 +3316,10 @@ bm::DetPostArgs detpost_args(const BoxMOTHipDetPost* handle, const void* d_pred,
     }
     return a;
 }
+// a mask handle is run with boxmot_hip_detpost_run_mask alone
+void detpost_refuse_mask(const BoxMOTHipDetPost* handle) {
+    if (handle && handle->mask_h) throw std::runtime_error("boxmot_hip: a detpost mask handle is run with boxmot_hip_detpost_run_mask");
+}
 // an untiled or a tiled run, by the handle's kind
 void detpost_run_checked(BoxMOTHipDetPost* handle, int n_streams, int dtype, const double* geom, const bm::DetPostArgs& a, void* hip_stream) {
     if (handle->n_tiles) {
@@ -3310,6 +3331,21 @@ void detpost_run_checked(BoxMOTHipDetPost* handle, int n_streams, int dtype, con
         std::vector<bm::DetPostGeom> g;
         detpost_geom_rows(geom, n_streams, g);
         detpost_run(handle, handle->geom, g, n_streams, hip_stream, [&](DetPostLaunch& on) { bm::detpost_launch(on, a, n_streams, dtype); });
+    }
+}
+// ... and of a mask handle: the same sequences with k_detpost_mask fourth (csrc/det_post_mask.hpp)
+void detpost_run_checked_mask(BoxMOTHipDetPost* handle, int n_streams, int dtype, const double* geom, const bm::DetPostArgs& a, const bm::DetPostMaskArgs& m,
+                              int proto_dtype, void* hip_stream) {
+    if (handle->n_tiles) {
+        const bm::DetPostTiledArgs ta{a, handle->tgeom.d, handle->n_tiles, handle->merge};
+        std::vector<bm::DetPostTileGeom> g;
+        detpost_tile_geom_rows(geom, n_streams, handle->n_tiles, g);
+        detpost_run(handle, handle->tgeom, g, n_streams, hip_stream,
+                    [&](DetPostLaunch& on) { bm::detpost_launch_tiled_with_mask(on, ta, m, n_streams, dtype, proto_dtype); });
+    } else {
+        std::vector<bm::DetPostGeom> g;
+        detpost_geom_rows(geom, n_streams, g);
+        detpost_run(handle, handle->geom, g, n_streams, hip_stream, [&](DetPostLaunch& on) { bm::detpost_launch_with_mask(on, a, m, n_streams, dtype, proto_dtype); });
     }
 }
 }  // namespace
@@ -3326,6 +3362,7 @@ void boxmot_hip_detpost_destroy(BoxMOTHipDetPost* handle) { destroy_on(handle); 
 int boxmot_hip_detpost_run(BoxMOTHipDetPost* handle, int n_streams, const void* d_pred, int dtype, const double* geom, float* d_dets,
                            int out_stride_rows, int* d_det_rows, void* hip_stream) {
     return guard_on(handle, [&]() {
+        detpost_refuse_mask(handle);
         detpost_check_run(handle, false, n_streams, d_pred, dtype, geom, d_dets, out_stride_rows, d_det_rows);
         detpost_run_checked(handle, n_streams, dtype, geom, detpost_args(handle, d_pred, d_dets, out_stride_rows, d_det_rows), hip_stream);
     });
@@ -3339,6 +3376,7 @@ BoxMOTHipDetPost* boxmot_hip_detpost_create_tiled(const BoxMOTHipDetPostTiledCon
 int boxmot_hip_detpost_run_tiled(BoxMOTHipDetPost* handle, int n_streams, const void* d_pred, int dtype, const double* geom, float* d_dets,
                                  int out_stride_rows, int* d_det_rows, void* hip_stream) {
     return guard_on(handle, [&]() {
+        detpost_refuse_mask(handle);
         detpost_check_run(handle, true, n_streams, d_pred, dtype, geom, d_dets, out_stride_rows, d_det_rows);
         detpost_run_checked(handle, n_streams, dtype, geom, detpost_args(handle, d_pred, d_dets, out_stride_rows, d_det_rows), hip_stream);
     });
@@ -3353,10 +3391,37 @@ BoxMOTHipDetPost* boxmot_hip_detpost_create_extra(const BoxMOTHipDetPostExtraCon
 int boxmot_hip_detpost_run_extra(BoxMOTHipDetPost* handle, int n_streams, const void* d_pred, int dtype, const double* geom, float* d_dets,
                                  int out_stride_rows, int* d_det_rows, float* d_extra, int* d_src, void* hip_stream) {
     return guard_on(handle, [&]() {
+        detpost_refuse_mask(handle);
         detpost_check_run(handle, handle && handle->n_tiles, n_streams, d_pred, dtype, geom, d_dets, out_stride_rows, d_det_rows, true);
         if (!d_extra) throw std::runtime_error("boxmot_hip: null detpost d_extra");
         if ((uintptr_t)d_extra % 4 || (uintptr_t)d_src % 4) throw std::runtime_error("boxmot_hip: detpost d_extra and d_src must be aligned to their element size");
         detpost_run_checked(handle, n_streams, dtype, geom, detpost_args(handle, d_pred, d_dets, out_stride_rows, d_det_rows, d_extra, d_src), hip_stream);
+    });
+}
+
+BoxMOTHipDetPost* boxmot_hip_detpost_create_mask(const BoxMOTHipDetPostMaskConfig* c) {
+    if (!c) { g_last_error = "boxmot_hip: null detpost config"; return nullptr; }
+    const BoxMOTHipDetPostTiledConfig tc{c->extra.base, c->extra.n_tiles, c->extra.merge};
+    return detpost_create(&c->extra.base, nullptr, c->extra.n_tiles ? &tc : nullptr, &c->extra, c);
+}
+
+int boxmot_hip_detpost_run_mask(BoxMOTHipDetPost* handle, int n_streams, const void* d_pred, int dtype, const double* geom, float* d_dets,
+                                int out_stride_rows, int* d_det_rows, float* d_extra, int* d_src, const void* d_proto, int proto_dtype,
+                                unsigned char* d_masks, void* hip_stream) {
+    return guard_on(handle, [&]() {
+        if (handle && !handle->mask_h) throw std::runtime_error("boxmot_hip: boxmot_hip_detpost_run_mask needs a handle of boxmot_hip_detpost_create_mask");
+        detpost_check_run(handle, handle && handle->n_tiles, n_streams, d_pred, dtype, geom, d_dets, out_stride_rows, d_det_rows, true);
+        if (!d_extra) throw std::runtime_error("boxmot_hip: null detpost d_extra");
+        if ((uintptr_t)d_extra % 4 || (uintptr_t)d_src % 4) throw std::runtime_error("boxmot_hip: detpost d_extra and d_src must be aligned to their element size");
+        if (!d_proto) throw std::runtime_error("boxmot_hip: null detpost d_proto");
+        if (!d_masks) throw std::runtime_error("boxmot_hip: null detpost d_masks");
+        if (proto_dtype != 0 && proto_dtype != 1)
+            throw std::runtime_error("boxmot_hip: unknown detpost proto_dtype " + std::to_string(proto_dtype) + " (0 fp32, 1 fp16)");
+        if ((uintptr_t)d_proto % (proto_dtype ? 2 : 4)) throw std::runtime_error("boxmot_hip: detpost d_proto must be aligned to its element size");
+        const int plane = handle->mask_h * handle->mask_w;
+        const bm::DetPostMaskArgs m{d_proto, d_masks, (long)handle->n_extra * plane, plane, handle->mask_h, handle->mask_w, handle->mask_wr, handle->mask_hr, 0};
+        detpost_run_checked_mask(handle, n_streams, dtype, geom, detpost_args(handle, d_pred, d_dets, out_stride_rows, d_det_rows, d_extra, d_src), m,
+                                 proto_dtype, hip_stream);
     });
 }
 

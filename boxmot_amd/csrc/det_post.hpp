@@ -35,7 +35,8 @@
 // The oriented layout "cn_obb" (layout 0 with obb = 1: one more channel row, the angle, after the classes; 7-column rows; rotated NMS)
 // is defined at the top of det_post_obb.hpp; it shares the score kernels, stages a-c and the kernel sequence below.
 // Heads with E more values per anchor after the class scores (pose keypoints, mask coefficients) are defined at the top of
-// det_post_extra.hpp: steps 1-6 read none of them, steps 7-8 write the source anchor and the extras of every emitted row.
+// det_post_extra.hpp: steps 1-6 read none of them, steps 7-8 write the source anchor and the extras of every emitted row.  Step 9,
+// the segmentation masks of the emitted rows from raw coefficients and the model's prototypes, is at the top of det_post_mask.hpp.
 // (Parity with torchvision / Ultralytics on real detector output is not pinned by any test: tests/detpost_ref.py restates this
 // definition in NumPy, and the kernels are compared with that, bit for bit.)
 //
@@ -63,6 +64,7 @@
 //          one of det_post_tiled.hpp have the same stage written out with their record, their "j suppresses i" and their row.
 //          dp_finish then writes d_det_rows and the counters (all three kernels).
 //   k_detpost_extra<T>   only on a head with extras (det_post_extra.hpp): third on the same stream, the extras of the emitted rows.
+//   k_detpost_mask<T, P> only on a mask handle (det_post_mask.hpp, which includes this file): fourth, the masks of the emitted rows.
 //   No floating-point atomic anywhere.  LDS: 8 + 16 + 4 + 1 bytes per candidate slot (K rounded up to a power of two) + 1.6 KB:
 //   31 KB at the default K = 1024, 118 KB at K = 4096, of the 160 KB of a CU.
 #pragma once

@@ -1,6 +1,6 @@
 // Per-anchor extras through the detection post-processing (include/boxmot_hip.h, boxmot_hip_detpost_create_extra / _run_extra): pose
 // heads (Ultralytics *-pose: 17 keypoints x, y, visibility after the class scores, decoded to letterbox pixels) and segmentation
-// heads (*-seg: 32 mask coefficients; the prototype tensor and the masks stay the caller's) carry E more values per anchor.  The
+// heads (*-seg: 32 mask coefficients; det_post_mask.hpp decodes the masks from them, step 9) carry E more values per anchor.  The
 // rows of d_dets say nothing about the anchor they came from, so this writes, beside them and in the same row order, the source
 // anchor and the extras of every emitted row -- d_extra[s][det_ind] is then the skeleton or the coefficients of the detection a
 // track was matched to.  Included by det_post.hpp.

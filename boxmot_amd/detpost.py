@@ -50,7 +50,25 @@ the top of csrc/det_post_extra.hpp); the tracker's ``det_ind`` column then finds
 Stated plainly: ``"kpt2"`` / ``"kpt3"`` map x and y to the frame with the arithmetic of the boxes, ``clip((v - left) / gain, 0, cols)``
 (tiled: the row's own tile, clipped to it, then shifted), and copy the visibility; ``"raw"`` copies.  A NaN coordinate comes out as 0.
 This is a reading of Ultralytics' ``scale_coords`` + ``clip_coords``, pinned against this repository's NumPy restatement
-(tests/detpost_extra_ref.py) only.  Mask decoding (coefficients x prototypes) stays the caller's.  Not for ``"cn_obb"``.
+(tests/detpost_extra_ref.py) only.  Not for ``"cn_obb"``.
+
+Segmentation masks: ``DetPost(..., extra=32, mask=(mask_h, mask_w), in_shape=(in_h, in_w))`` also decodes the masks of the emitted
+rows on the device, from the ``"raw"`` coefficients and the model's prototype tensor (the definition is at the top of
+csrc/det_post_mask.hpp); ``d_masks[s][det_ind]`` is then the mask of a track, as ``d_extra[s][det_ind]`` is its coefficients:
+
+    post = DetPost(S, n_anchors=8400, n_classes=80, layout="cn", extra=32, mask=(160, 160), in_shape=(640, 640), max_det=256)
+    d_coef = torch.empty((S, 256, 32), device="cuda"); d_masks = torch.empty((S, 256, 160, 160), dtype=torch.uint8, device="cuda")
+    pred, proto = seg_model(x)                                          # (S, 4 + 80 + 32, 8400) and (S, 32, 160, 160), fp16 or fp32 each
+    post.run(pred, geo, d_dets, d_rows, hip_stream=st, d_extra=d_coef, d_proto=proto, d_masks=d_masks)
+    masks_of_tracks = d_masks[s][d_out[s, :n_out, 7].long()]
+
+Stated plainly: a mask byte is 1 where the pixel lies in the row's letterbox-space box scaled to the prototypes' size -- ``x1 * wr <= j
+< x2 * wr``, ``y1 * hr <= i < y2 * hr`` in float32, ``wr = mask_w / in_w``, ``hr = mask_h / in_h``, Ultralytics ``crop_mask``'s ``>=`` /
+``<`` -- and ``sum_k coef[k] * proto[k, i, j] > 0``, a float32 chain over ascending ``k`` without fused multiply-add; else 0.  The mask
+is at PROTOTYPE resolution in letterbox space (tiled: the letterbox of the row's own tile, ``d_src // n_anchors``, whose prototypes
+are used): bilinear upsampling to the input or the frame size (``upsample=True``, ``scale_masks``) stays the caller's.  This is a
+reading of ``process_mask(..., upsample=False)``, pinned against this repository's NumPy restatement (tests/detpost_mask_ref.py)
+only, not against Ultralytics.  No masks for ``"cn_obb"``.
 """
 from __future__ import annotations
 
@@ -66,6 +84,8 @@ MERGES = {"iou": 0, "ios": 1}
 MAX_TILES = 64
 EXTRA_KINDS = {"raw": 0, "kpt2": 1, "kpt3": 2}
 MAX_EXTRA = 1024
+MAX_MASK_EXTRA = 256
+MAX_MASK_DIM = 1024
 _DTYPES = {"float32": 0, "float16": 1}
 
 
@@ -107,7 +127,7 @@ class DetPost:
     def __init__(self, n_streams: int, n_anchors: int, n_classes: int, layout: str = "cn", conf: float = 0.25, iou: float = 0.45,
                  max_det: int = 256, max_candidates: int = 1024, agnostic: bool = False, classes=None, nms: str | None = None,
                  regularize: bool | None = None, tiles: int | None = None, merge: str | None = None, extra: int | None = None,
-                 extra_kind: str | None = None):
+                 extra_kind: str | None = None, mask=None, in_shape=None):
         """``layout``: ``"cn"`` -- (S, 4 + n_classes, n_anchors), the Ultralytics v8 / 11 raw head, conf = the best class score --
         ``"nc_obj"`` -- (S, n_anchors, 5 + n_classes), the YOLOX / YOLOv5 decoded head, conf = obj * the best class score -- or
         ``"cn_obb"`` -- (S, 4 + n_classes + 1, n_anchors), the Ultralytics OBB raw head, the angle in radians as the last row.
@@ -118,10 +138,14 @@ class DetPost:
         intersection over the smaller box; ``n_anchors`` stays the anchors of ONE tile tensor.  Not for ``"cn_obb"``.
         ``extra``: the head has that many more values per anchor after the class scores (1..1024) and ``run`` also writes
         ``d_extra`` / ``d_src``; ``extra_kind``: ``"raw"`` (the default) copies them, ``"kpt2"`` / ``"kpt3"`` map keypoints (x, y /
-        x, y, visibility) to the frame.  With ``tiles`` or without; not for ``"cn_obb"``."""
+        x, y, visibility) to the frame.  With ``tiles`` or without; not for ``"cn_obb"``.
+        ``mask=(mask_h, mask_w)`` (1..1024 each) with ``in_shape=(in_h, in_w)``, the detector's input size: the ``extra`` (1..256)
+        values are ``"raw"`` mask coefficients and ``run`` also takes the prototypes ``d_proto`` and writes ``d_masks``, uint8 at
+        prototype resolution in letterbox space.  Stated plainly: upsampling stays the caller's; pinned against this
+        repository's NumPy restatement only.  With ``tiles`` or without; not for ``"cn_obb"``."""
         self._handle = None
         self._configure(n_streams, n_anchors, n_classes, layout, conf, iou, max_det, max_candidates, agnostic, classes, nms, regularize, tiles, merge,
-                        extra, extra_kind)
+                        extra, extra_kind, mask, in_shape)
         self._lib = _lib.load()
         allow = None
         if self.classes is not None:
@@ -129,7 +153,11 @@ class DetPost:
             allow[self.classes] = 1
         cfg = _lib.DetPostConfig(self.n_streams, self.n_anchors, self.n_classes, LAYOUTS[self.layout], self.conf, self.iou, self.max_candidates,
                                  self.max_det, int(self.agnostic), None if allow is None else allow.ctypes.data)
-        if self.extra is not None:
+        if self.mask is not None:
+            ecfg = _lib.DetPostExtraConfig(cfg, self.tiles or 0, MERGES[self.merge or "iou"], self.extra, EXTRA_KINDS[self.extra_kind])
+            mcfg = _lib.DetPostMaskConfig(ecfg, self.mask[0], self.mask[1], self.in_shape[0], self.in_shape[1])
+            self._handle = self._lib.boxmot_hip_detpost_create_mask(ctypes.byref(mcfg))
+        elif self.extra is not None:
             ecfg = _lib.DetPostExtraConfig(cfg, self.tiles or 0, MERGES[self.merge or "iou"], self.extra, EXTRA_KINDS[self.extra_kind])
             self._handle = self._lib.boxmot_hip_detpost_create_extra(ctypes.byref(ecfg))
         elif self.tiles is not None:
@@ -144,7 +172,7 @@ class DetPost:
             raise RuntimeError(_lib.last_error())
 
     def _configure(self, n_streams, n_anchors, n_classes, layout="cn", conf=0.25, iou=0.45, max_det=256, max_candidates=1024, agnostic=False,
-                   classes=None, nms=None, regularize=None, tiles=None, merge=None, extra=None, extra_kind=None):
+                   classes=None, nms=None, regularize=None, tiles=None, merge=None, extra=None, extra_kind=None, mask=None, in_shape=None):
         """the options, checked; touches neither the library nor a device"""
         for name, v in (("n_streams", n_streams), ("n_anchors", n_anchors), ("n_classes", n_classes), ("max_det", max_det)):
             if int(v) != v or int(v) < 1:
@@ -164,6 +192,8 @@ class DetPost:
             merge = "iou" if merge is None else merge
             if merge not in MERGES:
                 raise ValueError(f"DetPost: unknown merge {merge!r} (\"iou\" or \"ios\")")
+        if mask is not None and is_obb:
+            raise ValueError("DetPost: layout \"cn_obb\" has no masks: mask= is for \"cn\" and \"nc_obj\"")
         if extra is None and extra_kind is not None:
             raise ValueError("DetPost: extra_kind= belongs to a head with extras: give extra= as well")
         if extra is not None:
@@ -177,6 +207,24 @@ class DetPost:
             group = {"raw": 1, "kpt2": 2, "kpt3": 3}[extra_kind]
             if int(extra) % group:
                 raise ValueError(f"DetPost: extra_kind {extra_kind!r} takes values in groups of {group}: extra = {extra} is no multiple")
+        if mask is None and in_shape is not None:
+            raise ValueError("DetPost: in_shape= belongs to a mask handle: give mask= as well")
+        if mask is not None:
+            if extra is None:
+                raise ValueError("DetPost: mask= needs extra=, the number of mask coefficients per anchor")
+            if in_shape is None:
+                raise ValueError("DetPost: mask= needs in_shape=(in_h, in_w), the detector's input size")
+            if extra_kind != "raw":
+                raise ValueError(f"DetPost: mask= takes extra_kind \"raw\" (the mask coefficients), not extra_kind {extra_kind!r}")
+            if int(extra) > MAX_MASK_EXTRA:
+                raise ValueError(f"DetPost: mask= takes extra within 1..{MAX_MASK_EXTRA}, got {extra!r}")
+            for name, v, hi in (("mask", mask, MAX_MASK_DIM), ("in_shape", in_shape, None)):
+                try:
+                    ok = len(v) == 2 and all(int(q) == q and int(q) >= 1 and (hi is None or int(q) <= hi) for q in v)
+                except (TypeError, ValueError):
+                    ok = False
+                if not ok:
+                    raise ValueError(f"DetPost: {name} must be two integers " + (f"within 1..{hi}" if hi else ">= 1") + f", got {v!r}")
         nms = "greedy" if nms is None else nms
         if nms not in NMS_MODES:
             raise ValueError(f"DetPost: unknown nms {nms!r} (\"greedy\" or \"fast\")")
@@ -199,6 +247,7 @@ class DetPost:
         self.n_channels = (5 + self.n_classes if is_obb or layout == "nc_obj" else 4 + self.n_classes) + (self.extra or 0)    # per anchor, in the layout
         self.det_cols = 7 if is_obb else 6
         self.tiles, self.merge = (None, None) if tiles is None else (int(tiles), merge)
+        self.mask, self.in_shape = (None, None) if mask is None else ((int(mask[0]), int(mask[1])), (int(in_shape[0]), int(in_shape[1])))
 
     def pred_shape(self, n: int | None = None) -> tuple:
         n = (self.n_streams if n is None else n) * (self.tiles or 1)
@@ -271,7 +320,38 @@ class DetPost:
             table = np.array([_geometry_row(g, s) for s, g in enumerate(geo)], dtype=np.float64)
         return n, dtype, table, dshape[1]
 
-    def run(self, pred, geo, d_dets, d_det_rows, hip_stream: int = 0, d_extra=None, d_src=None) -> None:
+    def _check_mask(self, n, rows, d_proto, d_masks):
+        """the prototype dtype code of a call over ``n`` streams into blocks of ``rows`` rows per stream, or None on a handle without
+        masks; raises ValueError naming what is wrong"""
+        if self.mask is None:
+            if d_proto is not None or d_masks is not None:
+                raise ValueError("DetPost.run: d_proto and d_masks belong to a mask handle (mask=), which this one is not")
+            return None
+        if d_proto is None or d_masks is None:
+            raise ValueError(f"DetPost.run: a handle of mask={self.mask} needs d_proto and d_masks")
+        T = self.tiles or 1
+        want = (self.extra,) + self.mask
+        pshape = tuple(int(v) for v in d_proto.shape)
+        if len(pshape) != 4 or pshape[0] < n * T or pshape[1:] != want:
+            raise ValueError(f"DetPost.run: d_proto must have shape {('N >= %d' % (n * T),) + want}, got {pshape}")
+        pdtype = _DTYPES.get(_dtype_name(d_proto))
+        if pdtype is None:
+            raise ValueError(f"DetPost.run: d_proto must be float16 or float32, got {d_proto.dtype}")
+        if not d_proto.is_contiguous():
+            raise ValueError("DetPost.run: d_proto must be contiguous")
+        mshape = tuple(int(v) for v in d_masks.shape)
+        if len(mshape) != 4 or mshape[0] < n or mshape[1] != rows or mshape[2:] != self.mask:
+            raise ValueError(f"DetPost.run: d_masks must have shape {('N >= %d' % n, rows) + self.mask}, the rows of d_dets, got {mshape}")
+        if _dtype_name(d_masks) != "uint8":
+            raise ValueError(f"DetPost.run: d_masks must be uint8, got {d_masks.dtype}")
+        if not d_masks.is_contiguous():
+            raise ValueError("DetPost.run: d_masks must be contiguous")
+        for name, t in (("d_proto", d_proto), ("d_masks", d_masks)):
+            if not int(t.data_ptr()):
+                raise ValueError(f"DetPost.run: {name} has a null device address")
+        return pdtype
+
+    def run(self, pred, geo, d_dets, d_det_rows, hip_stream: int = 0, d_extra=None, d_src=None, d_proto=None, d_masks=None) -> None:
         """``pred``: the detector's raw output of the first ``len(geo)`` streams, a contiguous float16 / float32 device tensor in
         the handle's layout -- anything with ``data_ptr()``, ``dtype``, ``shape`` and ``is_contiguous()``; ``geo``: what
         ``FrameRing.letterbox`` returned for them; ``d_dets``: (N, rows >= max_det, 6) float32, ``d_det_rows``: (N,) int32, on the
@@ -282,8 +362,18 @@ class DetPost:
         ``T`` ``TileGeometry`` (or 7-sequences gain, top, left, x0, y0, w, h); ``d_dets`` / ``d_det_rows`` stay per stream.
         A handle of ``extra=E``: ``d_extra`` (N, rows of d_dets, E) float32 takes the extras of every row and, where given,
         ``d_src`` (N, rows of d_dets) int32 the anchor it came from (tiled: ``t * n_anchors + a``); rows beyond the count are left
-        alone there too."""
+        alone there too.  A handle of ``mask=(mask_h, mask_w)``: ``d_proto`` (N, E, mask_h, mask_w) float16 / float32, one tensor per
+        stream (tiled: per (stream, tile), like ``pred``), and ``d_masks`` (N, rows of d_dets, mask_h, mask_w) uint8, which takes
+        the 0 / 1 mask of every row at prototype resolution in letterbox space; both required there, refused elsewhere."""
         n, dtype, table, stride = self._check_run(pred, geo, d_dets, d_det_rows, d_extra, d_src)
+        pdtype = self._check_mask(n, stride, d_proto, d_masks)
+        if pdtype is not None:
+            _lib.check(self._lib.boxmot_hip_detpost_run_mask(
+                self._handle, n, ctypes.c_void_p(int(pred.data_ptr())), dtype, table.ctypes.data_as(_lib.c_double_p),
+                ctypes.c_void_p(int(d_dets.data_ptr())), stride, ctypes.c_void_p(int(d_det_rows.data_ptr())), ctypes.c_void_p(int(d_extra.data_ptr())),
+                None if d_src is None else ctypes.c_void_p(int(d_src.data_ptr())), ctypes.c_void_p(int(d_proto.data_ptr())), pdtype,
+                ctypes.c_void_p(int(d_masks.data_ptr())), ctypes.c_void_p(int(hip_stream))))
+            return
         if self.extra is not None:
             _lib.check(self._lib.boxmot_hip_detpost_run_extra(
                 self._handle, n, ctypes.c_void_p(int(pred.data_ptr())), dtype, table.ctypes.data_as(_lib.c_double_p),
@@ -295,13 +385,20 @@ class DetPost:
                        table.ctypes.data_as(_lib.c_double_p), ctypes.c_void_p(int(d_dets.data_ptr())), stride,
                        ctypes.c_void_p(int(d_det_rows.data_ptr())), ctypes.c_void_p(int(hip_stream))))
 
-    def run_host(self, pred, geo) -> list:
+    def run_host(self, pred, geo, proto=None) -> list:
         """Convenience form: ``pred`` a device tensor or a host array (uploaded); returns the rows of each stream as an (n_s, 6)
         float32 array, (n_s, 7) for layout ``"cn_obb"``; on a handle of ``extra=E`` a tuple ``(rows, extras (n_s, E) float32, src (n_s,)
-        int32)`` per stream.  Allocates its outputs with torch and waits for the result."""
+        int32)`` per stream; on a handle of ``mask=`` ``proto`` (a device tensor or a host array) is needed and the tuple is ``(rows,
+        extras, src, masks (n_s, mask_h, mask_w) uint8)``.  Allocates its outputs with torch and waits for the result."""
         import torch
         if isinstance(pred, np.ndarray):
             pred = torch.from_numpy(np.ascontiguousarray(pred)).cuda()
+        if self.mask is None and proto is not None:
+            raise ValueError("DetPost.run_host: proto belongs to a mask handle (mask=), which this one is not")
+        if self.mask is not None and proto is None:
+            raise ValueError(f"DetPost.run_host: a handle of mask={self.mask} needs proto")
+        if isinstance(proto, np.ndarray):
+            proto = torch.from_numpy(np.ascontiguousarray(proto)).to(pred.device)
         n = len(geo)
         d_dets = torch.empty((max(n, 1), self.max_det, self.det_cols), dtype=torch.float32, device=pred.device)
         d_rows = torch.zeros(max(n, 1), dtype=torch.int32, device=pred.device)
@@ -313,6 +410,12 @@ class DetPost:
             return [dets[s, :rows[s]].copy() for s in range(n)]
         d_extra = torch.empty((max(n, 1), self.max_det, self.extra), dtype=torch.float32, device=pred.device)
         d_src = torch.empty((max(n, 1), self.max_det), dtype=torch.int32, device=pred.device)
+        if self.mask is not None:
+            d_masks = torch.empty((max(n, 1), self.max_det) + self.mask, dtype=torch.uint8, device=pred.device)
+            self.run(pred, geo, d_dets, d_rows, hip_stream=st.cuda_stream, d_extra=d_extra, d_src=d_src, d_proto=proto, d_masks=d_masks)
+            st.synchronize()
+            rows, dets, extras, src = d_rows.cpu().numpy(), d_dets.cpu().numpy(), d_extra.cpu().numpy(), d_src.cpu().numpy()
+            return [(dets[s, :rows[s]].copy(), extras[s, :rows[s]].copy(), src[s, :rows[s]].copy(), d_masks[s, :rows[s]].cpu().numpy()) for s in range(n)]
         self.run(pred, geo, d_dets, d_rows, hip_stream=st.cuda_stream, d_extra=d_extra, d_src=d_src)
         st.synchronize()
         rows, dets, extras, src = d_rows.cpu().numpy(), d_dets.cpu().numpy(), d_extra.cpu().numpy(), d_src.cpu().numpy()

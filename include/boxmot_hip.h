@@ -491,6 +491,24 @@ BoxMOTHipDetPost* boxmot_hip_detpost_create_extra(const BoxMOTHipDetPostExtraCon
 int boxmot_hip_detpost_run_extra(BoxMOTHipDetPost* handle, int n_streams, const void* d_pred, int dtype, const double* geom, float* d_dets,
                                  int out_stride_rows, int* d_det_rows, float* d_extra, int* d_src /* may be null */, void* hip_stream);
 
+/* Segmentation masks of the emitted rows (csrc/det_post_mask.hpp has the full definition): a mask handle is an extras handle with
+ * extra.extra_kind 0 "raw" and extra.n_extra = E (1..256) mask coefficients per anchor, plus the prototypes' size mask_h, mask_w
+ * (1..1024 each) and the detector's input size in_h, in_w (>= 1).  run_mask does everything run_extra does and then writes, for
+ * every emitted row, the uint8 plane d_masks[s][row][mask_h][mask_w]: 1 where the pixel lies inside the row's letterbox-space box
+ * scaled by mask_w / in_w and mask_h / in_h (x1 <= j < x2, y1 <= i < y2, in float32) and sum_k coefficient[k] * proto[k][i][j] > 0
+ * (float32, k ascending, no fused multiply-add), else 0.  d_proto: a contiguous (n_streams [* n_tiles], E, mask_h, mask_w) tensor,
+ * proto_dtype 0 fp32 / 1 fp16 independently of dtype, aligned to its element size; a tiled row uses the prototypes of its own tile,
+ * tensor s * n_tiles + d_src / n_anchors.  The masks are at PROTOTYPE resolution in letterbox (tile-letterbox) space: upsampling to
+ * the input or the frame size stays the caller's.  Rows at and beyond d_det_rows[s] are not touched.  Such a handle is run with
+ * run_mask only -- boxmot_hip_detpost_run / _run_tiled / _run_extra refuse it, as run_mask refuses any other handle -- and read and
+ * destroyed with boxmot_hip_detpost_counters / _destroy.  Pinned against this repository's NumPy restatement only, not against
+ * Ultralytics.  The oriented layout has no masks. */
+typedef struct BoxMOTHipDetPostMaskConfig { BoxMOTHipDetPostExtraConfig extra; int mask_h, mask_w, in_h, in_w; } BoxMOTHipDetPostMaskConfig;
+BoxMOTHipDetPost* boxmot_hip_detpost_create_mask(const BoxMOTHipDetPostMaskConfig* config);
+int boxmot_hip_detpost_run_mask(BoxMOTHipDetPost* handle, int n_streams, const void* d_pred, int dtype, const double* geom, float* d_dets,
+                                int out_stride_rows, int* d_det_rows, float* d_extra, int* d_src /* may be null */,
+                                const void* d_proto, int proto_dtype, unsigned char* d_masks /* [n][out_stride_rows][mask_h][mask_w] */, void* hip_stream);
+
 /* ------------------------------------------------------------------------------------------------
  * DeepOCSORT (boxmot/trackers/bbox/deepocsort/deepocsort.py:235-492).  The reference has no native backend
  * for this tracker; the entry points follow the BoT-SORT ones above (same buffer, error and ownership

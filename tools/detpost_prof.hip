@@ -7,12 +7,17 @@
 //
 //     hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -o detpost_prof tools/detpost_prof.hip
 //     ./detpost_prof pred.bin [streams = 16] [anchors = 8400] [classes = 80] [layout = 0] [fp16 = 1] [K = 1024] [max_det = 256] [repeats = 30]
-//                   [obb = 0] [nms_mode = 0] [extra = 0] [extra_kind = 0]
+//                   [obb = 0] [nms_mode = 0] [extra = 0] [extra_kind = 0] [mask_h = 0] [mask_w = 0] [in_h = 0] [in_w = 0] [proto.bin]
 // pred.bin: ONE stream's tensor, (4 + nc, A) or (A, 5 + nc), raw; every stream gets a copy.  obb = 1: the oriented layout
 // (det_post_obb.hpp), (4 + nc + 1, A) with layout 0, nms_mode 0 greedy / 1 fast; the host copies are not timed again.  conf 0.25, iou 0.45, class-aware,
 // geometry of a 1080 x 1920 frame in a centred 640 x 640 letterbox.  extra = E > 0: a head with E more values per anchor
 // (det_post_extra.hpp), (4 + nc + E, A) or (A, 5 + nc + E): the three-kernel sequence -- score, the select kernel's source-storing
 // variant, k_detpost_extra -- a line for the third kernel, and the sums of stream 0's extras and source anchors in the checksum.
+// mask_h > 0 (with extra = E, extra_kind 0): a mask handle's four-kernel sequence (det_post_mask.hpp); proto.bin is ONE stream's
+// (E, mask_h, mask_w) fp16 prototypes, every stream gets a copy.  A line for k_detpost_mask, one for a hipMemsetAsync of exactly the
+// emitted mask bytes (streams x rows x mask_h x mask_w, into a block of its own) timed in the same calls -- the floor of a kernel
+// that must write those bytes -- one for the device-to-host copy of the prototypes, and in the checksum the sum of stream 0's mask
+// bytes and a position-weighted sum of them.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -21,7 +26,7 @@
 #include <cstring>
 #include <vector>
 
-#include "../boxmot_amd/csrc/det_post.hpp"
+#include "../boxmot_amd/csrc/det_post_mask.hpp"
 
 #define CHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { std::fprintf(stderr, "%s: %s\n", #x, hipGetErrorString(e_)); return 1; } } while (0)
 
@@ -32,7 +37,7 @@ static void report(const char* name, std::vector<float> ms) {
 
 struct TimedLaunch {            // every kernel of the sequence between its own pair of events
     hipStream_t stream;
-    hipEvent_t* ev;             // [6]: up to three kernels
+    hipEvent_t* ev;             // [8]: up to four kernels
     int k = 0;
     template <class K, class... A>
     void operator()(K kernel, int gx, int gy, int threads, size_t lds_bytes, A... args) {
@@ -47,7 +52,12 @@ int main(int argc, char** argv) {
     auto arg = [&](int k, int d) { return argc > k ? std::atoi(argv[k]) : d; };
     if (argc < 2) { std::fprintf(stderr, "usage: detpost_prof pred.bin [streams anchors classes layout fp16 K max_det repeats]\n"); return 1; }
     const int S = arg(2, 16), A = arg(3, 8400), nc = arg(4, 80), layout = arg(5, 0), fp16 = arg(6, 1), K = arg(7, 1024), max_det = arg(8, 256), reps = arg(9, 30),
-              obb = arg(10, 0), mode = arg(11, 0), cols = obb ? 7 : 6, E = arg(12, 0), kind = arg(13, 0);
+              obb = arg(10, 0), mode = arg(11, 0), cols = obb ? 7 : 6, E = arg(12, 0), kind = arg(13, 0), mh = arg(14, 0), mw = arg(15, 0), in_h = arg(16, 0),
+              in_w = arg(17, 0);
+    if (mh && (!E || kind != 0 || E > bm::DP_MASK_E_MAX || mh < 1 || mh > bm::DP_MASK_DIM_MAX || mw < 1 || mw > bm::DP_MASK_DIM_MAX || in_h < 1 || in_w < 1 || argc < 19)) {
+        std::fprintf(stderr, "masks: extra within 1..256 of extra_kind 0, mask_h and mask_w within 1..1024, in_h and in_w >= 1, and proto.bin\n");
+        return 1;
+    }
     if (E < 0 || E > bm::DP_EXTRA_MAX || kind < 0 || kind >= bm::DP_EXTRA_KINDS || (E && obb) || (E && E % bm::detpost_extra_group(kind))) {
         std::fprintf(stderr, "extra within 0..1024 and a multiple of its kind's group (0 raw, 1 kpt2, 2 kpt3); not with obb\n");
         return 1;
@@ -81,6 +91,21 @@ int main(int argc, char** argv) {
         CHECK(hipMalloc(&d_src, (size_t)S * max_det * 4));
         CHECK(hipMemset(d_extra, 0, (size_t)S * max_det * E * 4));
     }
+    const size_t plane = (size_t)mh * mw, proto_per = (size_t)E * plane * 2, proto_bytes = proto_per * S, mask_bytes = (size_t)S * max_det * plane;
+    void *d_proto = nullptr, *h_proto = nullptr;
+    uint8_t *d_masks = nullptr, *d_yard = nullptr;
+    if (mh) {
+        std::vector<unsigned char> one_proto(proto_per);
+        FILE* f = std::fopen(argv[18], "rb");
+        if (!f || std::fread(one_proto.data(), 1, proto_per, f) != proto_per) { std::fprintf(stderr, "%s: cannot read %zu bytes\n", argv[18], proto_per); return 1; }
+        std::fclose(f);
+        CHECK(hipMalloc(&d_proto, proto_bytes));
+        CHECK(hipMalloc(&d_masks, mask_bytes));
+        CHECK(hipMalloc(&d_yard, mask_bytes));
+        CHECK(hipMemset(d_masks, 0xA5, mask_bytes));
+        CHECK(hipHostMalloc(&h_proto, proto_bytes, hipHostMallocDefault));
+        for (int s = 0; s < S; ++s) CHECK(hipMemcpy((unsigned char*)d_proto + proto_per * s, one_proto.data(), proto_per, hipMemcpyHostToDevice));
+    }
     CHECK(hipHostMalloc(&h_pinned, bytes, hipHostMallocDefault));
     std::vector<unsigned char> h_pageable(bytes);
     for (int s = 0; s < S; ++s) CHECK(hipMemcpy((unsigned char*)d_pred + per * s, one.data(), per, hipMemcpyHostToDevice));
@@ -102,36 +127,52 @@ int main(int argc, char** argv) {
     CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     bm::DetPostArgs a{d_pred, d_geom, nullptr, d_keys, d_cls, d_dets, d_rows, d_counters, A, nc, layout, K, max_det, 0, max_det, 0.25f, 0.45f, obb, mode, 0};
     if (E) { a.src = d_src; a.extra = d_extra; a.src_stride = max_det; a.n_extra = E; a.extra_kind = kind; }
-    constexpr int EV = 10;          // events per timed call: three kernel pairs, two copy pairs
+    const bm::DetPostMaskArgs m{d_proto, d_masks, (long)E * (long)plane, (int)plane, mh, mw, mh ? (float)mw / (float)in_w : 0.f, mh ? (float)mh / (float)in_h : 0.f, 0};
+    auto sequence = [&](TimedLaunch& on) { if (mh) bm::detpost_launch_with_mask(on, a, m, S, fp16, 1); else bm::detpost_launch(on, a, S, fp16); };
+    constexpr int EV = 16;          // events per timed call: four kernel pairs, two copy pairs, the memset, the prototypes' copy
     std::vector<hipEvent_t> ev(EV * (size_t)reps);
     for (auto& e : ev) CHECK(hipEventCreate(&e));
-    for (int k = 0; k < 5; ++k) { TimedLaunch warm{st, ev.data()}; bm::detpost_launch(warm, a, S, fp16); }
+    for (int k = 0; k < 5; ++k) { TimedLaunch warm{st, ev.data()}; sequence(warm); }
     CHECK(hipGetLastError());
     CHECK(hipStreamSynchronize(st));
+    int n = 0;                      // stream 0's rows: every stream holds the same tensor
+    CHECK(hipMemcpy(&n, d_rows, 4, hipMemcpyDeviceToHost));
+    const size_t emitted = (size_t)S * n * plane;
     for (int k = 0; k < reps; ++k) {
         hipEvent_t* e = &ev[EV * (size_t)k];
         TimedLaunch tl{st, e};
-        bm::detpost_launch(tl, a, S, fp16);
+        sequence(tl);
         if (obb) { CHECK(hipStreamSynchronize(st)); continue; }
-        CHECK(hipEventRecord(e[6], st)); CHECK(hipMemcpyAsync(h_pinned, d_pred, bytes, hipMemcpyDeviceToHost, st)); CHECK(hipEventRecord(e[7], st));
+        CHECK(hipEventRecord(e[8], st)); CHECK(hipMemcpyAsync(h_pinned, d_pred, bytes, hipMemcpyDeviceToHost, st)); CHECK(hipEventRecord(e[9], st));
         CHECK(hipStreamSynchronize(st));
-        CHECK(hipEventRecord(e[8], st)); CHECK(hipMemcpyAsync(h_pageable.data(), d_pred, bytes, hipMemcpyDeviceToHost, st)); CHECK(hipEventRecord(e[9], st));
+        CHECK(hipEventRecord(e[10], st)); CHECK(hipMemcpyAsync(h_pageable.data(), d_pred, bytes, hipMemcpyDeviceToHost, st)); CHECK(hipEventRecord(e[11], st));
         CHECK(hipStreamSynchronize(st));
+        if (mh) {
+            CHECK(hipEventRecord(e[12], st)); if (emitted) CHECK(hipMemsetAsync(d_yard, 0, emitted, st)); CHECK(hipEventRecord(e[13], st));
+            CHECK(hipStreamSynchronize(st));
+            CHECK(hipEventRecord(e[14], st)); CHECK(hipMemcpyAsync(h_proto, d_proto, proto_bytes, hipMemcpyDeviceToHost, st)); CHECK(hipEventRecord(e[15], st));
+            CHECK(hipStreamSynchronize(st));
+        }
     }
     CHECK(hipGetLastError());
-    std::vector<float> t_score(reps), t_select(reps), t_both(reps), t_pin(reps), t_page(reps), t_extra(reps), t_three(reps);
+    std::vector<float> t_score(reps), t_select(reps), t_both(reps), t_pin(reps), t_page(reps), t_extra(reps), t_three(reps), t_mask(reps), t_four(reps), t_set(reps),
+        t_proto(reps);
     for (int k = 0; k < reps; ++k) {
         hipEvent_t* e = &ev[EV * (size_t)k];
         CHECK(hipEventElapsedTime(&t_score[k], e[0], e[1]));
         CHECK(hipEventElapsedTime(&t_select[k], e[2], e[3]));
         CHECK(hipEventElapsedTime(&t_both[k], e[0], e[3]));
         if (E) { CHECK(hipEventElapsedTime(&t_extra[k], e[4], e[5])); CHECK(hipEventElapsedTime(&t_three[k], e[0], e[5])); }
+        if (mh) {
+            CHECK(hipEventElapsedTime(&t_mask[k], e[6], e[7])); CHECK(hipEventElapsedTime(&t_four[k], e[0], e[7]));
+            CHECK(hipEventElapsedTime(&t_set[k], e[12], e[13])); CHECK(hipEventElapsedTime(&t_proto[k], e[14], e[15]));
+        }
         if (obb) continue;
-        CHECK(hipEventElapsedTime(&t_pin[k], e[6], e[7]));
-        CHECK(hipEventElapsedTime(&t_page[k], e[8], e[9]));
+        CHECK(hipEventElapsedTime(&t_pin[k], e[8], e[9]));
+        CHECK(hipEventElapsedTime(&t_page[k], e[10], e[11]));
     }
     std::vector<float> rows((size_t)max_det * cols);
-    int n = 0, counters[bm::DP_COUNTERS];
+    int counters[bm::DP_COUNTERS];
     CHECK(hipMemcpy(&n, d_rows, 4, hipMemcpyDeviceToHost));
     CHECK(hipMemcpy(counters, d_counters, sizeof(counters), hipMemcpyDeviceToHost));
     CHECK(hipMemcpy(rows.data(), d_dets, rows.size() * 4, hipMemcpyDeviceToHost));
@@ -147,6 +188,13 @@ int main(int argc, char** argv) {
         report("k_detpost_extra", t_extra);
         report("all three kernels", t_three);
     }
+    if (mh) {
+        std::printf("(masks %d x %d of a %d x %d input, fp16 prototypes %.2f MB; %d rows per stream: %zu mask bytes emitted)\n", mh, mw, in_h, in_w, proto_bytes * 1e-6, n, emitted);
+        report("k_detpost_mask", t_mask);
+        report("all four kernels", t_four);
+        report("memset of those bytes", t_set);
+        report("D2H of proto, pinned", t_proto);
+    }
     if (!obb) {
         report("D2H of pred, pinned", t_pin);
         report("D2H of pred, pageable", t_page);
@@ -160,6 +208,15 @@ int main(int argc, char** argv) {
         long ssum = 0;
         for (int k = 0; k < n * E; ++k) esum += ex[k];
         for (int k = 0; k < n; ++k) ssum += src[k];
+        if (mh) {                   // ... and stream 0's masks
+            std::vector<uint8_t> mk((size_t)n * plane);
+            CHECK(hipMemcpy(mk.data(), d_masks, mk.size(), hipMemcpyDeviceToHost));
+            long msum = 0, wsum = 0;
+            for (size_t k = 0; k < mk.size(); ++k) { msum += mk[k]; wsum += (long)mk[k] * (long)(k % 251 + 1); }
+            std::printf("checksum: rows %d counters %d %d %d sum %.6f extra %.6f src %ld mask %ld weighted %ld\n", n, counters[0], counters[1], counters[2], sum, esum,
+                        ssum, msum, wsum);
+            return 0;
+        }
         std::printf("checksum: rows %d counters %d %d %d sum %.6f extra %.6f src %ld\n", n, counters[0], counters[1], counters[2], sum, esum, ssum);
         return 0;
     }

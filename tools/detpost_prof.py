@@ -18,8 +18,15 @@ variant, k_detpost_extra -- with the third kernel's useful bytes per second (wha
 element of the tensor and one float32, per row one source index), beside the host path it replaces, the copy of the tensor plus
 tests/detpost_extra_ref.py on this host.  The checksum covers the rows, the extras and the source anchors.
 
-Needs a gfx950 device.  profiles/detpost_timing.txt, profiles/detpost_obb_timing.txt and profiles/detpost_extra_timing.txt hold the
-outputs of such runs."""
+``--mask`` times a SEGMENTATION head with the masks decoded on the device (csrc/det_post_mask.hpp): A = 8400 anchors, 80 classes, E =
+32 coefficients, fp16, "cn", 64 streams, prototypes 32 x 160 x 160 fp16 of a 640 x 640 input, a quiet and a busy scene; the
+four-kernel sequence with k_detpost_mask between its own events, beside a hipMemsetAsync of exactly the emitted mask bytes timed in
+the same calls (the floor of a kernel that must write them), k_detpost_mask's useful bytes per second (the mask bytes stored plus
+the prototype bytes inside the windows), and the host path it replaces: the copy of the prototypes plus tests/detpost_mask_ref.py
+on this host.  The checksum covers the rows, the extras, the source anchors and stream 0's masks.
+
+Needs a gfx950 device.  profiles/detpost_timing.txt, profiles/detpost_obb_timing.txt, profiles/detpost_extra_timing.txt and
+profiles/detpost_mask_timing.txt hold the outputs of such runs."""
 import argparse
 import os
 import subprocess
@@ -34,7 +41,8 @@ ROOT = Path(__file__).resolve().parent.parent
 SRC = ROOT / "tools" / "detpost_prof.hip"
 EXE = ROOT / "tools" / "_build" / "detpost_prof"
 CSRC = ROOT / "boxmot_amd" / "csrc"
-DEPS = [SRC, CSRC / "det_post.hpp", CSRC / "det_post_obb.hpp", CSRC / "det_post_extra.hpp", CSRC / "det_post_select_body.hpp", CSRC / "kernel_macros.hpp"]
+DEPS = [SRC, CSRC / "det_post.hpp", CSRC / "det_post_obb.hpp", CSRC / "det_post_extra.hpp", CSRC / "det_post_select_body.hpp", CSRC / "kernel_macros.hpp",
+        CSRC / "det_post_mask.hpp", CSRC / "det_post_tiled.hpp", CSRC / "det_post_tiled_select_body.hpp"]
 sys.path[:0] = [str(ROOT / "tests"), str(ROOT)]          # the reference lives with the tests
 
 
@@ -148,6 +156,53 @@ def main_extra(exe, a, out) -> int:
     return 0
 
 
+def main_mask(exe, a, out) -> int:
+    import detpost_extra_ref as eref
+    import detpost_mask_ref as mref
+    import detpost_ref as ref
+    A, nc, E, K, max_det, S, mask, in_shape = 8400, 80, 32, 1024, 256, 64, (160, 160), (640, 640)
+    geo = ref.GEO_CENTER
+    rng = np.random.default_rng(3)
+    proto = mref.vals(rng, (1, E) + mask).astype(np.float16)
+    proto_path = out / "detpost_mask_proto.bin"
+    proto.tofile(proto_path)
+    for name, rate in (("quiet", 0.01), ("busy", 0.3)):
+        pred = eref.with_extras(ref.random_pred(A, nc, "cn", np.float16, 1, rate, n_obj=60), "cn", mref.vals(rng, (A, E)), np.float16)
+        path = out / f"detpost_mask_pred_{name}.bin"
+        pred.tofile(path)
+        times = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            rows, counters, extras, src = eref.detpost_extra(pred, geo, "cn", nc, E, "raw", 0.25, 0.45, max_det, K)
+            masks = mref.step9(pred[None], proto, "cn", A, rows, extras, src, mask, in_shape, False)
+            times.append(time.perf_counter() - t0)
+        flat = masks.reshape(-1).astype(np.int64)
+        want = checksum(rows, counters) + f" extra {float(extras.astype(np.float64).sum()):.6f} src {int(src.astype(np.int64).sum())}" + \
+            f" mask {int(flat.sum())} weighted {int((flat * (np.arange(flat.size) % 251 + 1)).sum())}"
+        inside = sum(int(mref.window_of(mref.box_of(pred, "cn", int(an)), mask, in_shape).sum()) for an in src)
+        print(f"== {name} scene (pass rate {rate}): {counters[0]} of {A} anchors pass, {counters[1]} candidates, {counters[2]} kept by NMS, {len(rows)} rows; "
+              f"{inside} of {len(rows) * mask[0] * mask[1]} mask pixels inside their windows, {int(flat.sum())} set", flush=True)
+        print(f"NumPy reference of ONE stream on this host (tests/detpost_extra_ref.py + detpost_mask_ref.py): median {1e3 * sorted(times)[1]:.2f} ms of 3", flush=True)
+        r = subprocess.run([str(exe), str(path), *[str(v) for v in (S, A, nc, 0, 1, K, max_det, a.repeats, 0, 0, E, 0, mask[0], mask[1], in_shape[0], in_shape[1])],
+                            str(proto_path)], capture_output=True, text=True, timeout=300)
+        print(r.stdout, end="", flush=True)
+        if r.returncode != 0:
+            print(r.stderr, file=sys.stderr)
+            return r.returncode or 1
+        got = [ln for ln in r.stdout.splitlines() if ln.startswith("checksum:")][0]
+        if got != want:
+            print(f"CHECKSUM MISMATCH: device `{got}`, reference `{want}`", file=sys.stderr)
+            return 1
+        print("checksum equals the reference's", flush=True)
+        med = {key: [float(ln.split("median")[1].split("us")[0]) for ln in r.stdout.splitlines() if ln.startswith(key)][0] for key in ("k_detpost_mask", "memset of those bytes")}
+        stored, loaded = S * len(rows) * mask[0] * mask[1], S * inside * E * proto.itemsize
+        print(f"k_detpost_mask: {stored} mask bytes stored + {loaded} prototype bytes inside the windows = {stored + loaded} useful bytes in "
+              f"{med['k_detpost_mask']:.1f} us: {(stored + loaded) / med['k_detpost_mask'] * 1e-3:.1f} GB/s; the memset of the {stored} mask bytes alone "
+              f"{med['memset of those bytes']:.1f} us ({stored / max(med['memset of those bytes'], 1e-9) * 1e-3:.1f} GB/s): ratio "
+              f"{med['k_detpost_mask'] / max(med['memset of those bytes'], 1e-9):.2f}", flush=True)
+    return 0
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--streams", type=int, nargs="+", default=[1, 16, 64])
@@ -157,10 +212,15 @@ def main() -> int:
     ap.add_argument("--build-only", action="store_true", help="compile the measuring program and stop (no device needed)")
     ap.add_argument("--obb", action="store_true", help="the oriented layout beside the axis-aligned one at 64 x 21504 x 15 (see above)")
     ap.add_argument("--extra", action="store_true", help="a pose head, 64 x 8400 x (4 + 1 + 51): the three-kernel sequence with extras (see above)")
+    ap.add_argument("--mask", action="store_true", help="a segmentation head, 64 x 8400 x (4 + 80 + 32) with 32 x 160 x 160 prototypes: the four-kernel sequence (see above)")
     a = ap.parse_args()
     exe = build()
     if a.build_only:
         return 0
+    if a.mask:
+        out = Path(a.out) if a.out else Path(tempfile.mkdtemp())
+        out.mkdir(parents=True, exist_ok=True)
+        return main_mask(exe, a, out)
     if a.extra:
         out = Path(a.out) if a.out else Path(tempfile.mkdtemp())
         out.mkdir(parents=True, exist_ok=True)
