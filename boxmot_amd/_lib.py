@@ -279,6 +279,7 @@ SIGNATURES = {
     "boxmot_hip_detpost_run_extra": (_I, [_VP, _I, _VP, _I, c_double_p, _VP, _I, _VP, _VP, _VP, _VP]),
     "boxmot_hip_detpost_create_mask": (_VP, [ctypes.POINTER(DetPostMaskConfig)]),
     "boxmot_hip_detpost_run_mask": (_I, [_VP, _I, _VP, _I, c_double_p, _VP, _I, _VP, _VP, _VP, _VP, _I, _VP, _VP]),
+    "boxmot_hip_detpost_labels": (_I, [_VP, _I, c_double_p, _VP, _I, _VP, _I, _VP, _VP, _VP, _I, _I, _VP]),
     "boxmot_hip_last_error": (ctypes.c_char_p, []),
     "boxmot_hip_device_count": (_I, []),
     "boxmot_hip_botsort_device": (_I, [_VP]),

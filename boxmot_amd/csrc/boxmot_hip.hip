@@ -29,6 +29,7 @@
 #include "det_post.hpp"
 #include "det_post_tiled.hpp"
 #include "det_post_mask.hpp"
+#include "det_post_labels.hpp"
 
 namespace {
 
@@ -3422,6 +3423,54 @@ int boxmot_hip_detpost_run_mask(BoxMOTHipDetPost* handle, int n_streams, const v
         const bm::DetPostMaskArgs m{d_proto, d_masks, (long)handle->n_extra * plane, plane, handle->mask_h, handle->mask_w, handle->mask_wr, handle->mask_hr, 0};
         detpost_run_checked_mask(handle, n_streams, dtype, geom, detpost_args(handle, d_pred, d_dets, out_stride_rows, d_det_rows, d_extra, d_src), m,
                                  proto_dtype, hip_stream);
+    });
+}
+
+int boxmot_hip_detpost_labels(BoxMOTHipDetPost* handle, int n_streams, const double* geom, const void* d_proto, int proto_dtype, const float* d_dets,
+                              int det_stride, const int* d_det_rows, const float* d_extra, short* d_labels, int label_rows, int label_cols,
+                              void* hip_stream) {
+    return guard_on(handle, [&]() {
+        if (!handle) throw std::runtime_error("boxmot_hip: null detpost handle");
+        const BoxMOTHipDetPostConfig& c = handle->cfg;
+        if (!handle->mask_h) throw std::runtime_error("boxmot_hip: boxmot_hip_detpost_labels needs a handle of boxmot_hip_detpost_create_mask");
+        if (handle->n_tiles)
+            throw std::runtime_error("boxmot_hip: boxmot_hip_detpost_labels takes an untiled mask handle: label maps of tiled handles are out of scope");
+        if (c.max_det > bm::DP_LABEL_MAX_DET)
+            throw std::runtime_error("boxmot_hip: boxmot_hip_detpost_labels writes int16 labels: max_det " + std::to_string(c.max_det) + " exceeds " +
+                                     std::to_string(bm::DP_LABEL_MAX_DET));
+        if (n_streams < 1 || n_streams > c.n_streams)
+            throw std::runtime_error("boxmot_hip: detpost stream count " + std::to_string(n_streams) + " out of range for a handle of " + std::to_string(c.n_streams));
+        if (!geom) throw std::runtime_error("boxmot_hip: null detpost geom");
+        if (!d_proto) throw std::runtime_error("boxmot_hip: null detpost d_proto");
+        if (!d_dets) throw std::runtime_error("boxmot_hip: null detpost d_dets");
+        if (!d_det_rows) throw std::runtime_error("boxmot_hip: null detpost d_det_rows");
+        if (!d_extra) throw std::runtime_error("boxmot_hip: null detpost d_extra");
+        if (!d_labels) throw std::runtime_error("boxmot_hip: null detpost d_labels");
+        if (proto_dtype != 0 && proto_dtype != 1)
+            throw std::runtime_error("boxmot_hip: unknown detpost proto_dtype " + std::to_string(proto_dtype) + " (0 fp32, 1 fp16)");
+        if ((uintptr_t)d_proto % (proto_dtype ? 2 : 4) || (uintptr_t)d_dets % 4 || (uintptr_t)d_det_rows % 4 || (uintptr_t)d_extra % 4 || (uintptr_t)d_labels % 2)
+            throw std::runtime_error("boxmot_hip: detpost device addresses must be aligned to their element size");
+        if (det_stride < c.max_det)
+            throw std::runtime_error("boxmot_hip: detpost det_stride " + std::to_string(det_stride) + " is below max_det " + std::to_string(c.max_det));
+        if (label_rows < 1 || label_cols < 1 || (long)label_rows * label_cols > (1L << 30))
+            throw std::runtime_error("boxmot_hip: detpost label_rows x label_cols must be at least 1 x 1 and at most 2^30 pixels, got " +
+                                     std::to_string(label_rows) + " x " + std::to_string(label_cols));
+        std::vector<bm::DetPostGeom> g;
+        detpost_geom_rows(geom, n_streams, g);
+        int frame_rows = 1, frame_cols = 1;
+        for (int s = 0; s < n_streams; ++s) {
+            if (g[s].rows > (float)label_rows || g[s].cols > (float)label_cols)
+                throw std::runtime_error("boxmot_hip: detpost stream " + std::to_string(s) + ": the frame of " + std::to_string((long)g[s].rows) + " x " +
+                                         std::to_string((long)g[s].cols) + " does not fit label planes of " + std::to_string(label_rows) + " x " +
+                                         std::to_string(label_cols));
+            if ((int)g[s].rows > frame_rows) frame_rows = (int)g[s].rows;
+            if ((int)g[s].cols > frame_cols) frame_cols = (int)g[s].cols;
+        }
+        const int plane = handle->mask_h * handle->mask_w;
+        const bm::DetPostLabelArgs a{handle->geom.d, d_proto, d_dets, d_det_rows, d_extra, reinterpret_cast<int16_t*>(d_labels), (long)handle->n_extra * plane, (long)label_rows * label_cols,
+                                     label_cols, det_stride, c.max_det, handle->n_extra, handle->mask_h, handle->mask_w, plane, handle->mask_wr, handle->mask_hr,
+                                     0, 0};
+        detpost_run(handle, handle->geom, g, n_streams, hip_stream, [&](DetPostLaunch& on) { bm::detpost_launch_labels(on, a, n_streams, frame_rows, frame_cols, proto_dtype); });
     });
 }
 

@@ -69,6 +69,24 @@ is at PROTOTYPE resolution in letterbox space (tiled: the letterbox of the row's
 are used): bilinear upsampling to the input or the frame size (``upsample=True``, ``scale_masks``) stays the caller's.  This is a
 reading of ``process_mask(..., upsample=False)``, pinned against this repository's NumPy restatement (tests/detpost_mask_ref.py)
 only, not against Ultralytics.  No masks for ``"cn_obb"``.
+
+Frame-space label map: on an UNTILED mask handle ``labels`` turns the rows of a run into one int16 plane per stream at FRAME
+resolution -- every pixel the row of ``d_dets`` that owns it, the tracker's ``det_ind``, or -1 (the definition is at the top of
+csrc/det_post_labels.hpp) -- 4 MB per 1080p stream where dense per-row frame masks would take 530 MB:
+
+    post.run(pred, geo, d_dets, d_rows, hip_stream=st, d_extra=d_coef, d_proto=proto, d_masks=d_masks)
+    post.labels(geo, proto, d_dets, d_rows, d_coef, d_labels, hip_stream=st)                  # d_labels: (S, 1080, 1920) int16
+    trk.step_device(d_dets.data_ptr(), d_rows.data_ptr(), ...)
+    lut = torch.full((257,), -1.0, device="cuda"); lut[d_out[s, :n_out, 7].long()] = d_out[s, :n_out, 4]
+    track_ids = lut[d_labels[s].long()]                               # lut[-1] is the last entry: no track
+
+Stated plainly: a row covers a frame pixel when the pixel lies in the row's FRAME box (``x1 <= x < x2``, ``y1 <= y < y2``) and the
+row's float logits, sampled bilinearly where the pixel's centre falls in the prototype plane -- ``pu = ((x + 0.5) * gain + left) * wr
+- 0.5`` clamped to the plane, likewise ``pv`` -- are ``> 0``: upsampled before thresholding (``process_mask_native``'s order), every
+float32 operation rounded on its own; the smallest such row wins, so the highest confidence does.  This is the exact inverse of the
+handle's letterbox map with half-pixel centres composed with ``align_corners=False`` sampling; it is NOT Ultralytics ``scale_masks``'
+integer-cropped interpolation, which shifts by a fraction of a prototype pixel, and it is pinned against this repository's NumPy
+restatement (tests/detpost_labels_ref.py) only.  Out of scope: tiled handles, ``"cn_obb"``, dense per-row frame masks, polygons.
 """
 from __future__ import annotations
 
@@ -86,6 +104,7 @@ EXTRA_KINDS = {"raw": 0, "kpt2": 1, "kpt3": 2}
 MAX_EXTRA = 1024
 MAX_MASK_EXTRA = 256
 MAX_MASK_DIM = 1024
+MAX_LABEL_DET = 32767
 _DTYPES = {"float32": 0, "float16": 1}
 
 
@@ -420,6 +439,104 @@ class DetPost:
         st.synchronize()
         rows, dets, extras, src = d_rows.cpu().numpy(), d_dets.cpu().numpy(), d_extra.cpu().numpy(), d_src.cpu().numpy()
         return [(dets[s, :rows[s]].copy(), extras[s, :rows[s]].copy(), src[s, :rows[s]].copy()) for s in range(n)]
+
+    def _check_labels(self, geo, d_proto, d_dets, d_det_rows, d_extra, d_labels):
+        """(n_streams, prototype dtype code, geometry table, rows per stream of d_dets, label_rows, label_cols) of a ``labels`` call;
+        raises ValueError naming what is wrong"""
+        if self.mask is None:
+            raise ValueError("DetPost.labels: label maps belong to a mask handle (mask=), which this one is not")
+        if self.tiles is not None:
+            raise ValueError("DetPost.labels: label maps of a tiled handle (tiles=) are out of scope: use an untiled mask handle")
+        if self.max_det > MAX_LABEL_DET:
+            raise ValueError(f"DetPost.labels: the labels are int16: max_det = {self.max_det} exceeds {MAX_LABEL_DET}")
+        n = len(geo)
+        if not 1 <= n <= self.n_streams:
+            raise ValueError(f"DetPost.labels: geo has {n} entries for a handle of {self.n_streams} streams")
+        want = (self.extra,) + self.mask
+        pshape = tuple(int(v) for v in d_proto.shape)
+        if len(pshape) != 4 or pshape[0] < n or pshape[1:] != want:
+            raise ValueError(f"DetPost.labels: d_proto must have shape {('N >= %d' % n,) + want}, got {pshape}")
+        pdtype = _DTYPES.get(_dtype_name(d_proto))
+        if pdtype is None:
+            raise ValueError(f"DetPost.labels: d_proto must be float16 or float32, got {d_proto.dtype}")
+        dshape = tuple(int(v) for v in d_dets.shape)
+        if len(dshape) != 3 or dshape[0] < n or dshape[2] != self.det_cols:
+            raise ValueError(f"DetPost.labels: d_dets must have shape (N >= {n}, rows, {self.det_cols}), got {dshape}")
+        if dshape[1] < self.max_det:
+            raise ValueError(f"DetPost.labels: d_dets holds {dshape[1]} rows per stream, fewer than max_det = {self.max_det}")
+        if _dtype_name(d_dets) != "float32":
+            raise ValueError(f"DetPost.labels: d_dets must be float32, got {d_dets.dtype}")
+        rshape = tuple(int(v) for v in d_det_rows.shape)
+        if len(rshape) != 1 or rshape[0] < n:
+            raise ValueError(f"DetPost.labels: d_det_rows must have shape (N >= {n},), got {rshape}")
+        if _dtype_name(d_det_rows) != "int32":
+            raise ValueError(f"DetPost.labels: d_det_rows must be int32, got {d_det_rows.dtype}")
+        eshape = tuple(int(v) for v in d_extra.shape)
+        if len(eshape) != 3 or eshape[0] < n or eshape[1] != dshape[1] or eshape[2] != self.extra:
+            raise ValueError(f"DetPost.labels: d_extra must have shape (N >= {n}, {dshape[1]}, {self.extra}), the rows of d_dets, got {eshape}")
+        if _dtype_name(d_extra) != "float32":
+            raise ValueError(f"DetPost.labels: d_extra must be float32, got {d_extra.dtype}")
+        lshape = tuple(int(v) for v in d_labels.shape)
+        if len(lshape) != 3 or lshape[0] < n or lshape[1] < 1 or lshape[2] < 1:
+            raise ValueError(f"DetPost.labels: d_labels must have shape (N >= {n}, H, W), got {lshape}")
+        if _dtype_name(d_labels) != "int16":
+            raise ValueError(f"DetPost.labels: d_labels must be int16, got {d_labels.dtype}")
+        for name, t in (("d_proto", d_proto), ("d_dets", d_dets), ("d_det_rows", d_det_rows), ("d_extra", d_extra), ("d_labels", d_labels)):
+            if not t.is_contiguous():
+                raise ValueError(f"DetPost.labels: {name} must be contiguous")
+            if not int(t.data_ptr()):
+                raise ValueError(f"DetPost.labels: {name} has a null device address")
+        table = np.array([_geometry_row(g, s) for s, g in enumerate(geo)], dtype=np.float64)
+        for s, row in enumerate(table):
+            if row[3] > lshape[1] or row[4] > lshape[2]:
+                raise ValueError(f"DetPost.labels: stream {s}: the frame of {int(row[3])} x {int(row[4])} does not fit d_labels' planes of {lshape[1]} x {lshape[2]}")
+        return n, pdtype, table, dshape[1], lshape[1], lshape[2]
+
+    def labels(self, geo, d_proto, d_dets, d_det_rows, d_extra, d_labels, hip_stream: int = 0) -> None:
+        """The frame-space instance label map of the rows a ``run`` on the same stream left in ``d_dets`` / ``d_det_rows`` /
+        ``d_extra`` (the definition is step 10 at the top of csrc/det_post_labels.hpp); an untiled mask handle only.  ``geo`` and
+        ``d_proto`` are the run's; ``d_labels``: (N >= len(geo), H, W) int16 with H, W at least every stream's frame.  Asynchronous on
+        ``hip_stream``: ``d_labels[s, y, x]`` for every pixel of stream ``s``'s frame becomes the smallest row ``r < min(d_det_rows[s],
+        max_det)`` that covers it -- ``x1 <= x < x2``, ``y1 <= y < y2`` on the row's frame box and the row's logits, sampled bilinearly
+        at the pixel centre's position in the prototype plane, ``> 0`` -- or -1; the rest of a larger plane and streams beyond
+        ``len(geo)`` are left alone.  Stated plainly: the exact inverse of the letterbox map with half-pixel centres composed with
+        ``align_corners=False`` sampling, NOT Ultralytics ``scale_masks``' integer-cropped interpolation; pinned against this
+        repository's NumPy restatement only."""
+        n, pdtype, table, stride, rows, cols = self._check_labels(geo, d_proto, d_dets, d_det_rows, d_extra, d_labels)
+        _lib.check(self._lib.boxmot_hip_detpost_labels(
+            self._handle, n, table.ctypes.data_as(_lib.c_double_p), ctypes.c_void_p(int(d_proto.data_ptr())), pdtype, ctypes.c_void_p(int(d_dets.data_ptr())),
+            stride, ctypes.c_void_p(int(d_det_rows.data_ptr())), ctypes.c_void_p(int(d_extra.data_ptr())), ctypes.c_void_p(int(d_labels.data_ptr())), rows, cols,
+            ctypes.c_void_p(int(hip_stream))))
+
+    def labels_host(self, pred, geo, proto) -> list:
+        """Convenience form beside ``run_host``: ``run`` then ``labels`` on the current torch stream; returns per stream a tuple ``(rows,
+        extras, src, labels (frame rows, frame cols) int16)``.  ``pred`` / ``proto``: device tensors or host arrays (uploaded).
+        Allocates its outputs with torch and waits for the result."""
+        import torch
+        if self.mask is None:
+            raise ValueError("DetPost.labels_host: label maps belong to a mask handle (mask=), which this one is not")
+        if self.tiles is not None:
+            raise ValueError("DetPost.labels_host: label maps of a tiled handle (tiles=) are out of scope: use an untiled mask handle")
+        if isinstance(pred, np.ndarray):
+            pred = torch.from_numpy(np.ascontiguousarray(pred)).cuda()
+        if isinstance(proto, np.ndarray):
+            proto = torch.from_numpy(np.ascontiguousarray(proto)).to(pred.device)
+        n = len(geo)
+        table = [_geometry_row(g, s) for s, g in enumerate(geo)]
+        H, W = max([int(r[3]) for r in table] + [1]), max([int(r[4]) for r in table] + [1])
+        d_dets = torch.empty((max(n, 1), self.max_det, self.det_cols), dtype=torch.float32, device=pred.device)
+        d_rows = torch.zeros(max(n, 1), dtype=torch.int32, device=pred.device)
+        d_extra = torch.empty((max(n, 1), self.max_det, self.extra), dtype=torch.float32, device=pred.device)
+        d_src = torch.empty((max(n, 1), self.max_det), dtype=torch.int32, device=pred.device)
+        d_masks = torch.empty((max(n, 1), self.max_det) + self.mask, dtype=torch.uint8, device=pred.device)
+        d_labels = torch.empty((max(n, 1), H, W), dtype=torch.int16, device=pred.device)
+        st = torch.cuda.current_stream(pred.device)
+        self.run(pred, geo, d_dets, d_rows, hip_stream=st.cuda_stream, d_extra=d_extra, d_src=d_src, d_proto=proto, d_masks=d_masks)
+        self.labels(geo, proto, d_dets, d_rows, d_extra, d_labels, hip_stream=st.cuda_stream)
+        st.synchronize()
+        rows, dets, extras, src, labels = d_rows.cpu().numpy(), d_dets.cpu().numpy(), d_extra.cpu().numpy(), d_src.cpu().numpy(), d_labels.cpu().numpy()
+        return [(dets[s, :rows[s]].copy(), extras[s, :rows[s]].copy(), src[s, :rows[s]].copy(), labels[s, :int(table[s][3]), :int(table[s][4])].copy())
+                for s in range(n)]
 
     def counters(self) -> np.ndarray:
         """(n_streams, 3) int32 of the last run, after waiting for it: anchors that passed the threshold, candidates after the

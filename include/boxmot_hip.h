@@ -509,6 +509,22 @@ int boxmot_hip_detpost_run_mask(BoxMOTHipDetPost* handle, int n_streams, const v
                                 int out_stride_rows, int* d_det_rows, float* d_extra, int* d_src /* may be null */,
                                 const void* d_proto, int proto_dtype, unsigned char* d_masks /* [n][out_stride_rows][mask_h][mask_w] */, void* hip_stream);
 
+/* Frame-space instance label map from the rows of an UNTILED mask handle (csrc/det_post_labels.hpp has the full definition, step
+ * 10): after a run_mask on the same stream, d_labels[s][y][x], an int16 plane of label_rows x label_cols per stream, takes for every
+ * pixel of the stream's frame (geom's rows x cols) the smallest row r < min(d_det_rows[s], max_det) of d_dets[s] that covers it --
+ * the det_ind a tracker hands back -- or -1.  Row r covers (y, x) when x1 <= x < x2 and y1 <= y < y2 (the row's FRAME box, float32)
+ * and the row's logits, sampled bilinearly at the prototype position of the pixel's centre -- pu = ((x + 0.5) * gain + left) * wr -
+ * 0.5, clamped to the plane, likewise pv -- are > 0: upsampled before thresholding, every float32 operation rounded on its own.
+ * geom, d_proto, proto_dtype, d_dets, det_stride (= out_stride_rows), d_det_rows and d_extra are those of the run.  The pixels of a
+ * plane beyond the frame and streams beyond n_streams are left alone.  Stated plainly: the exact inverse of the handle's letterbox
+ * map with half-pixel centres composed with align_corners=False sampling -- NOT Ultralytics scale_masks' integer-cropped
+ * interpolation -- pinned against this repository's NumPy restatement only.  Refused: a handle that is not a mask handle, a tiled
+ * mask handle (out of scope), max_det > 32767, null pointers, planes smaller than a stream's frame.  No dense per-row frame masks,
+ * no polygons, nothing for the oriented layout. */
+int boxmot_hip_detpost_labels(BoxMOTHipDetPost* handle, int n_streams, const double* geom, const void* d_proto, int proto_dtype,
+                              const float* d_dets, int det_stride, const int* d_det_rows, const float* d_extra,
+                              short* d_labels /* [n][label_rows][label_cols] */, int label_rows, int label_cols, void* hip_stream);
+
 /* ------------------------------------------------------------------------------------------------
  * DeepOCSORT (boxmot/trackers/bbox/deepocsort/deepocsort.py:235-492).  The reference has no native backend
  * for this tracker; the entry points follow the BoT-SORT ones above (same buffer, error and ownership

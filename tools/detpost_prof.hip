@@ -18,6 +18,11 @@
 // emitted mask bytes (streams x rows x mask_h x mask_w, into a block of its own) timed in the same calls -- the floor of a kernel
 // that must write those bytes -- one for the device-to-host copy of the prototypes, and in the checksum the sum of stream 0's mask
 // bytes and a position-weighted sum of them.
+//     ./detpost_prof labels dets.bin coef.bin proto.bin n_rows streams E mask_h mask_w in_h in_w rows cols gain top left [repeats = 30]
+// the label-map kernel alone (det_post_labels.hpp): ONE stream's rows (n_rows, 6) float32 in frame coordinates, coefficients (n_rows, E)
+// float32 and (E, mask_h, mask_w) fp16 prototypes, every stream gets a copy; k_detpost_labels on the path it chooses (the LDS patch)
+// and with the fallback forced, in alternating blocks of five launches, each launch between its own pair of events.  The checksum is
+// the sum and a position-weighted sum of stream 0's labels; the two paths must give equal blocks.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -26,7 +31,7 @@
 #include <cstring>
 #include <vector>
 
-#include "../boxmot_amd/csrc/det_post_mask.hpp"
+#include "../boxmot_amd/csrc/det_post_labels.hpp"
 
 #define CHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { std::fprintf(stderr, "%s: %s\n", #x, hipGetErrorString(e_)); return 1; } } while (0)
 
@@ -48,7 +53,97 @@ struct TimedLaunch {            // every kernel of the sequence between its own 
     }
 };
 
+struct PlainLaunch {
+    hipStream_t stream;
+    template <class K, class... A>
+    void operator()(K kernel, int gx, int gy, int threads, size_t lds_bytes, A... args) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)gx, (unsigned)gy), dim3((unsigned)threads), lds_bytes, stream, args...);
+    }
+};
+
+template <class T>
+static bool read_file(const char* path, std::vector<T>& v) {
+    FILE* f = std::fopen(path, "rb");
+    const bool ok = f && std::fread(v.data(), sizeof(T), v.size(), f) == v.size();
+    if (f) std::fclose(f);
+    if (!ok) std::fprintf(stderr, "%s: cannot read %zu bytes\n", path, v.size() * sizeof(T));
+    return ok;
+}
+
+static int labels_main(int argc, char** argv) {
+    if (argc < 18) { std::fprintf(stderr, "usage: detpost_prof labels dets.bin coef.bin proto.bin n_rows streams E mask_h mask_w in_h in_w rows cols gain top left [repeats]\n"); return 1; }
+    const int n = std::atoi(argv[5]), S = std::atoi(argv[6]), E = std::atoi(argv[7]), mh = std::atoi(argv[8]), mw = std::atoi(argv[9]), in_h = std::atoi(argv[10]),
+              in_w = std::atoi(argv[11]), rows = std::atoi(argv[12]), cols = std::atoi(argv[13]), reps = argc > 17 ? std::atoi(argv[17]) : 30;
+    const float gain = (float)std::atof(argv[14]), top = (float)std::atof(argv[15]), left = (float)std::atof(argv[16]);
+    if (n < 1 || n > bm::DP_LABEL_MAX_DET || S < 1 || E < 1 || E > bm::DP_MASK_E_MAX || mh < 1 || mh > bm::DP_MASK_DIM_MAX || mw < 1 || mw > bm::DP_MASK_DIM_MAX || in_h < 1 ||
+        in_w < 1 || rows < 1 || cols < 1 || !(gain > 0.f) || reps < 10 || reps % 5) {
+        std::fprintf(stderr, "labels: n_rows within 1..32767, E within 1..256, mask within 1..1024, a frame of >= 1 x 1, gain > 0, repeats a multiple of 5\n");
+        return 1;
+    }
+    const size_t plane = (size_t)mh * mw, frame = (size_t)rows * cols;
+    std::vector<float> dets((size_t)n * 6), coef((size_t)n * E);
+    std::vector<_Float16> proto((size_t)E * plane);
+    if (!read_file(argv[2], dets) || !read_file(argv[3], coef) || !read_file(argv[4], proto)) return 1;
+    float *d_dets = nullptr, *d_coef = nullptr;
+    void* d_proto = nullptr;
+    int* d_rows = nullptr;
+    int16_t* d_labels[2] = {nullptr, nullptr};
+    bm::DetPostGeom* d_geom = nullptr;
+    CHECK(hipMalloc(&d_dets, (size_t)S * n * 6 * 4));
+    CHECK(hipMalloc(&d_coef, (size_t)S * n * E * 4));
+    CHECK(hipMalloc(&d_proto, (size_t)S * E * plane * 2));
+    CHECK(hipMalloc(&d_rows, (size_t)S * 4));
+    CHECK(hipMalloc(&d_geom, (size_t)S * sizeof(bm::DetPostGeom)));
+    for (int q = 0; q < 2; ++q) { CHECK(hipMalloc(&d_labels[q], (size_t)S * frame * 2)); CHECK(hipMemset(d_labels[q], 0xA5, (size_t)S * frame * 2)); }
+    std::vector<int> n_rows(S, n);
+    std::vector<bm::DetPostGeom> geom(S, bm::DetPostGeom{gain, top, left, (float)rows, (float)cols});
+    for (int s = 0; s < S; ++s) {
+        CHECK(hipMemcpy(d_dets + (size_t)s * n * 6, dets.data(), dets.size() * 4, hipMemcpyHostToDevice));
+        CHECK(hipMemcpy(d_coef + (size_t)s * n * E, coef.data(), coef.size() * 4, hipMemcpyHostToDevice));
+        CHECK(hipMemcpy((_Float16*)d_proto + (size_t)s * E * plane, proto.data(), proto.size() * 2, hipMemcpyHostToDevice));
+    }
+    CHECK(hipMemcpy(d_rows, n_rows.data(), (size_t)S * 4, hipMemcpyHostToDevice));
+    CHECK(hipMemcpy(d_geom, geom.data(), (size_t)S * sizeof(bm::DetPostGeom), hipMemcpyHostToDevice));
+    hipStream_t st;
+    CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    PlainLaunch on{st};
+    auto launch = [&](int fallback) {
+        const bm::DetPostLabelArgs a{d_geom, d_proto, d_dets, d_rows, d_coef, d_labels[fallback], (long)E * (long)plane, (long)frame, cols, n, n, E, mh, mw, (int)plane,
+                                     (float)mw / (float)in_w, (float)mh / (float)in_h, 0, fallback};
+        bm::detpost_launch_labels(on, a, S, rows, cols, 1);
+    };
+    for (int k = 0; k < 3; ++k) { launch(0); launch(1); }
+    CHECK(hipGetLastError());
+    CHECK(hipStreamSynchronize(st));
+    std::vector<hipEvent_t> ev(4 * (size_t)reps);
+    for (auto& e : ev) CHECK(hipEventCreate(&e));
+    for (int block = 0; block < reps / 5; ++block)
+        for (int fallback = 0; fallback < 2; ++fallback)
+            for (int k = 0; k < 5; ++k) {
+                hipEvent_t* e = &ev[4 * (size_t)(block * 5 + k) + 2 * fallback];
+                CHECK(hipEventRecord(e[0], st)); launch(fallback); CHECK(hipEventRecord(e[1], st));
+                CHECK(hipStreamSynchronize(st));
+            }
+    CHECK(hipGetLastError());
+    std::vector<float> t[2] = {std::vector<float>(reps), std::vector<float>(reps)};
+    for (int k = 0; k < reps; ++k)
+        for (int q = 0; q < 2; ++q) CHECK(hipEventElapsedTime(&t[q][k], ev[4 * (size_t)k + 2 * q], ev[4 * (size_t)k + 2 * q + 1]));
+    std::vector<int16_t> got[2] = {std::vector<int16_t>((size_t)S * frame), std::vector<int16_t>((size_t)S * frame)};
+    for (int q = 0; q < 2; ++q) CHECK(hipMemcpy(got[q].data(), d_labels[q], got[q].size() * 2, hipMemcpyDeviceToHost));
+    std::printf("%d streams of %d x %d frames, %d rows per stream, E %d, prototypes %d x %d fp16 of a %d x %d input, gain %.6f: %d x %d tiles per stream, labels %.2f MB\n", S, rows,
+                cols, n, E, mh, mw, in_h, in_w, gain, bm::detpost_label_tiles(cols, bm::DP_LABEL_TW), bm::detpost_label_tiles(rows, bm::DP_LABEL_TH), S * frame * 2e-6);
+    report("labels, LDS patch", t[0]);
+    report("labels, forced fallback", t[1]);
+    if (got[0] != got[1]) { std::fprintf(stderr, "the LDS path and the fallback path differ\n"); return 1; }
+    std::printf("the two paths give equal label blocks\n");
+    long sum = 0, wsum = 0, owned = 0;
+    for (size_t k = 0; k < frame; ++k) { sum += got[0][k]; wsum += (long)got[0][k] * (long)(k % 251 + 1); owned += got[0][k] >= 0; }
+    std::printf("checksum: labels sum %ld weighted %ld owned %ld\n", sum, wsum, owned);
+    return 0;
+}
+
 int main(int argc, char** argv) {
+    if (argc > 1 && !std::strcmp(argv[1], "labels")) return labels_main(argc, argv);
     auto arg = [&](int k, int d) { return argc > k ? std::atoi(argv[k]) : d; };
     if (argc < 2) { std::fprintf(stderr, "usage: detpost_prof pred.bin [streams anchors classes layout fp16 K max_det repeats]\n"); return 1; }
     const int S = arg(2, 16), A = arg(3, 8400), nc = arg(4, 80), layout = arg(5, 0), fp16 = arg(6, 1), K = arg(7, 1024), max_det = arg(8, 256), reps = arg(9, 30),

@@ -25,8 +25,16 @@ the same calls (the floor of a kernel that must write them), k_detpost_mask's us
 the prototype bytes inside the windows), and the host path it replaces: the copy of the prototypes plus tests/detpost_mask_ref.py
 on this host.  The checksum covers the rows, the extras, the source anchors and stream 0's masks.
 
-Needs a gfx950 device.  profiles/detpost_timing.txt, profiles/detpost_obb_timing.txt, profiles/detpost_extra_timing.txt and
-profiles/detpost_mask_timing.txt hold the outputs of such runs."""
+``--labels`` times the frame-space LABEL MAP (csrc/det_post_labels.hpp) through the public call, ``DetPost.labels``, between HIP events
+(torch.cuda.Event), medians of ``--repeats`` calls in alternating blocks of five with the path it replaces, timed in the same run: the
+torch-on-device sequence a caller writes today per stream -- ``coef @ proto``, the letterbox padding cut off, ``F.interpolate`` to
+the frame, crop to the row's box, ``> 0``, first-wins.  16 and 64 streams of 1080p, prototypes 32 x 160 x 160 fp16 of a 640 x 640
+input, a sparse scene (boxes covering about 0.3 x the frame area) and a busy one (about 2 x).  Then the measuring program runs the
+kernel alone on the LDS patch and with the fallback forced, alternating, and its checksum is compared with the public call's labels
+(and, on the sparse scene, with tests/detpost_labels_ref.py).  Reports; no threshold.
+
+Needs a gfx950 device.  profiles/detpost_timing.txt, profiles/detpost_obb_timing.txt, profiles/detpost_extra_timing.txt,
+profiles/detpost_mask_timing.txt and profiles/detpost_labels_timing.txt hold the outputs of such runs."""
 import argparse
 import os
 import subprocess
@@ -42,7 +50,7 @@ SRC = ROOT / "tools" / "detpost_prof.hip"
 EXE = ROOT / "tools" / "_build" / "detpost_prof"
 CSRC = ROOT / "boxmot_amd" / "csrc"
 DEPS = [SRC, CSRC / "det_post.hpp", CSRC / "det_post_obb.hpp", CSRC / "det_post_extra.hpp", CSRC / "det_post_select_body.hpp", CSRC / "kernel_macros.hpp",
-        CSRC / "det_post_mask.hpp", CSRC / "det_post_tiled.hpp", CSRC / "det_post_tiled_select_body.hpp"]
+        CSRC / "det_post_mask.hpp", CSRC / "det_post_labels.hpp", CSRC / "det_post_tiled.hpp", CSRC / "det_post_tiled_select_body.hpp"]
 sys.path[:0] = [str(ROOT / "tests"), str(ROOT)]          # the reference lives with the tests
 
 
@@ -203,6 +211,111 @@ def main_mask(exe, a, out) -> int:
     return 0
 
 
+def label_scene(rng, n, cover, frame):
+    """n rows [x1, y1, x2, y2, conf, cls] in frame coordinates, by descending confidence, whose boxes cover about ``cover`` times the frame area"""
+    rows, cols = frame
+    side = np.sqrt(cover * rows * cols / n)
+    w, h = side * rng.uniform(0.6, 1.4, n), side * rng.uniform(0.6, 1.4, n)
+    cx, cy = rng.uniform(0, cols, n), rng.uniform(0, rows, n)
+    box = np.stack([np.clip(cx - w / 2, 0, cols), np.clip(cy - h / 2, 0, rows), np.clip(cx + w / 2, 0, cols), np.clip(cy + h / 2, 0, rows)], 1)
+    box = np.round(box * 4) / 4
+    conf = np.sort(rng.uniform(0.3, 0.95, n))[::-1]
+    return np.concatenate([box, conf[:, None], rng.integers(0, 80, (n, 1))], 1).astype(np.float32)
+
+
+def torch_labels(torch, F, geo, in_shape, d_proto, d_dets, n, d_coef, d_labels):
+    """the path DetPost.labels replaces, as a caller writes it today with torch on the device, stream by stream"""
+    S, rows, cols = d_labels.shape
+    mh, mw = d_proto.shape[2:]
+    ys = torch.arange(rows, device="cuda", dtype=torch.float32)[None, :, None]
+    xs = torch.arange(cols, device="cuda", dtype=torch.float32)[None, None, :]
+    for s in range(S):
+        g = geo[s]
+        logits = (d_coef[s, :n] @ d_proto[s].float().view(d_proto.shape[1], -1)).view(n, mh, mw)
+        t, l = int(round(g.top * mh / in_shape[0])), int(round(g.left * mw / in_shape[1]))                      # scale_masks: the padding, in prototype pixels
+        logits = logits[:, t:mh - t, l:mw - l]
+        up = F.interpolate(logits[None], size=(rows, cols), mode="bilinear", align_corners=False)[0]
+        b = d_dets[s, :n, :4, None, None]
+        on = (up > 0) & (xs >= b[:, 0]) & (xs < b[:, 2]) & (ys >= b[:, 1]) & (ys < b[:, 3])
+        first = on.to(torch.uint8).argmax(0)                                                            # the first True, 0 where there is none
+        d_labels[s] = torch.where(on.any(0), first, torch.full_like(first, -1)).to(torch.int16)
+
+
+def main_labels(exe, a, out) -> int:
+    import torch
+    import torch.nn.functional as F
+    import detpost_labels_ref as lref
+    from boxmot_amd.detpost import DetPost
+    from boxmot_amd.ingest import letterbox_geometry
+    E, max_det, mask, in_shape, frame = 32, 256, (160, 160), (640, 640), (1080, 1920)
+    g = letterbox_geometry(frame[0], frame[1], in_shape)
+    g5 = (g.gain, g.top, g.left, g.rows, g.cols)
+    rng = np.random.default_rng(4)
+    proto = lref.vals(rng, (E,) + mask).astype(np.float16)
+    proto_path = out / "detpost_labels_proto.bin"
+    proto.tofile(proto_path)
+    reps = max(10, a.repeats // 5 * 5)
+    for name, n, cover in (("sparse", 24, 0.3), ("busy", 180, 2.0)):
+        dets, coef = label_scene(rng, n, cover, frame), lref.vals(rng, (n, E))
+        dets_path, coef_path = out / f"detpost_labels_dets_{name}.bin", out / f"detpost_labels_coef_{name}.bin"
+        dets.tofile(dets_path)
+        coef.tofile(coef_path)
+        area = float(((dets[:, 2] - dets[:, 0]) * (dets[:, 3] - dets[:, 1])).sum()) / (frame[0] * frame[1])
+        print(f"== {name} scene: {n} rows per stream, boxes covering {area:.2f} x the frame area", flush=True)
+        want = None
+        if name == "sparse":
+            t0 = time.perf_counter()
+            want = lref.labels_of(g5, dets, n, coef, proto, mask, in_shape, max_det)
+            print(f"NumPy reference of ONE stream on this host (tests/detpost_labels_ref.py): {time.perf_counter() - t0:.2f} s", flush=True)
+        for S in (16, 64):
+            post = DetPost(S, 8400, 80, extra=E, mask=mask, in_shape=in_shape, max_det=max_det)
+            d_proto = torch.from_numpy(proto).cuda()[None].repeat(S, 1, 1, 1).contiguous()
+            d_dets = torch.zeros((S, max_det, 6), device="cuda")
+            d_coef = torch.zeros((S, max_det, E), device="cuda")
+            d_dets[:, :n], d_coef[:, :n] = torch.from_numpy(dets).cuda(), torch.from_numpy(coef).cuda()
+            d_rows = torch.full((S,), n, dtype=torch.int32, device="cuda")
+            d_labels = torch.full((S,) + frame, -2, dtype=torch.int16, device="cuda")
+            d_other = torch.full((S,) + frame, -2, dtype=torch.int16, device="cuda")
+            st = torch.cuda.current_stream()
+            paths = {"DetPost.labels": lambda: post.labels([g] * S, d_proto, d_dets, d_rows, d_coef, d_labels, hip_stream=st.cuda_stream),
+                     "torch on the device": lambda: torch_labels(torch, F, [g] * S, in_shape, d_proto, d_dets, n, d_coef, d_other)}
+            for fn in paths.values():
+                fn(); fn()
+            torch.cuda.synchronize()
+            times = {k: [] for k in paths}
+            for block in range(reps // 5):
+                for key, fn in paths.items():
+                    for _ in range(5):
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record(st); fn(); e1.record(st)
+                        e1.synchronize()
+                        times[key].append(e0.elapsed_time(e1))
+            print(f"-- {S} streams of {frame[0]} x {frame[1]}, HIP events around the call, {reps} calls each in alternating blocks of 5", flush=True)
+            for key, v in times.items():
+                v = sorted(v)
+                print(f"{key:22s} median {1e3 * v[len(v) // 2]:.1f} us  min {1e3 * v[0]:.1f}  max {1e3 * v[-1]:.1f}  ({len(v)} samples)", flush=True)
+            med = {key: sorted(v)[len(v) // 2] for key, v in times.items()}
+            print(f"ratio torch / DetPost.labels: {med['torch on the device'] / med['DetPost.labels']:.1f}", flush=True)
+            lab, other = d_labels[0].cpu().numpy(), d_other[0].cpu().numpy()
+            assert all(torch.equal(d_labels[0], d_labels[s]) for s in range(1, S))
+            post.close()
+            print(f"pixels where the torch path (scale_masks' integer-cropped interpolation) agrees with the label map: {100.0 * float((lab == other).mean()):.2f} %", flush=True)
+            if want is not None and lab.tobytes() != want.tobytes():
+                print("LABELS DIFFER FROM THE REFERENCE", file=sys.stderr)
+                return 1
+            if want is not None:
+                print("the labels equal the reference's", flush=True)
+            flat = lab.reshape(-1).astype(np.int64)
+            checksum_want = f"checksum: labels sum {int(flat.sum())} weighted {int((flat * (np.arange(flat.size) % 251 + 1)).sum())} owned {int((flat >= 0).sum())}"
+            del d_proto, d_dets, d_coef, d_labels, d_other
+            torch.cuda.empty_cache()
+            status = run_exe(exe, ["labels", dets_path, coef_path, proto_path, n, S, E, mask[0], mask[1], in_shape[0], in_shape[1], frame[0], frame[1], repr(float(g.gain)),
+                                   repr(float(g.top)), repr(float(g.left)), reps], checksum_want)
+            if status:
+                return status
+    return 0
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--streams", type=int, nargs="+", default=[1, 16, 64])
@@ -213,10 +326,15 @@ def main() -> int:
     ap.add_argument("--obb", action="store_true", help="the oriented layout beside the axis-aligned one at 64 x 21504 x 15 (see above)")
     ap.add_argument("--extra", action="store_true", help="a pose head, 64 x 8400 x (4 + 1 + 51): the three-kernel sequence with extras (see above)")
     ap.add_argument("--mask", action="store_true", help="a segmentation head, 64 x 8400 x (4 + 80 + 32) with 32 x 160 x 160 prototypes: the four-kernel sequence (see above)")
+    ap.add_argument("--labels", action="store_true", help="the frame-space label map at 16 / 64 x 1080p beside the torch-on-device path it replaces (see above)")
     a = ap.parse_args()
     exe = build()
     if a.build_only:
         return 0
+    if a.labels:
+        out = Path(a.out) if a.out else Path(tempfile.mkdtemp())
+        out.mkdir(parents=True, exist_ok=True)
+        return main_labels(exe, a, out)
     if a.mask:
         out = Path(a.out) if a.out else Path(tempfile.mkdtemp())
         out.mkdir(parents=True, exist_ok=True)
